@@ -2,13 +2,25 @@
 per GPU per step (BASELINE.json configs[1]; N>1 = configs[3]-style utterance sharding with the
 output waveforms gathered to rank 0 over RCCL).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--seconds S] [--no-cpu-baseline] [--no-stream]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--seconds S] [--no-stream] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-per-call] [--no-roofline]
     python bench.py --gpus N --utterances 120 --seconds 30     # BASELINE configs[3]: 1 h over N GPUs
 
 Default: a clip stream (VC.pipeline_device_stream) -- K steps are K clips per GPU, clip k+1's front end
-(filtfilt, RMVPE, ContentVec) running on its own streams under clip k's synthesizer; the line also carries
-"per_call", the same K clips as one finished pipeline_device call each.  Each clip's output waveform is copied
-to pinned host memory inside the timed region (host-visible output; --hbm-output leaves it in HBM).
+(filtfilt, RMVPE, ContentVec) running on its own streams under clip k's synthesizer.  Each clip's output waveform is
+copied to pinned host memory inside the timed region (host-visible output; --hbm-output leaves it in
+HBM).  A plain run sets up, warms up, times the K steps and prints the line; "per_call", "roofline" and
+"cpu_baseline" are null in it.
+
+--full adds the measurements beside the headline figure, each a run of its own after the timed steps: "per_call"
+(the same K clips as one finished pipeline_device call each), "roofline" with its "families" (an instrumented pass
+and a torch.profiler pass) and "cpu_baseline" (the torch-CPU oracle); --no-per-call / --no-roofline /
+--no-cpu-baseline drop one of them from a --full run.
+
+--dump-outputs DIR writes, after the timed steps, the waveforms the last timed step handed back (one per clip of the
+step; --utterances: rank 0's gathered job) as DIR/waveform_<i>.npy, float32, at most 64 MB in all (beyond that a
+fixed seeded sample of each waveform's positions).  Inputs, weights and noise seeds depend only on the arguments, so
+two builds run with the same arguments can be compared output for output.
 
 --utterances U (BASELINE configs[3], SURVEY §8(d) cfg 4): a fixed job of U utterances of --seconds each (1 h =
 120 x 30 s), sharded longest-first over the ranks (rvc_amd.shard.shard_utterances), each rank's share issued as
@@ -20,7 +32,7 @@ gathered waveforms are the same bits at every world size (tests/test_gpu_shard.p
 child process, one rank per GPU); under an external launcher WORLD_SIZE must equal N.
 
 Prints ONE JSON line on rank 0 (contract in the task statement): metric/value = output
-audio-seconds per wall-second for the whole job, plus "roofline" for the dominant kernel
+audio-seconds per wall-second for the whole job, plus (--full) "roofline" for the dominant kernel
 family (the split-operand MFMA conv engine: conv_x6_kernel + the fused ResBlock pairs; algorithmic FLOPs over the
 device's own kernel stamps of one instrumented per-call pass, torch.profiler, with the HIP-event time beside it),
 its "families" (attention -- split-fp16 or f32 MFMA --, the BiGRU's us per step against its hand-off floor, and the HBM GB/s of
@@ -485,6 +497,22 @@ def cpu_baseline(seconds=30.0):
                             "(profiles/cpu_calibration.json)") if cal else None}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, waveforms):
+    """Write the 1-D waveforms as path/waveform_<i>.npy (float32).  Beyond DUMP_LIMIT_BYTES in all, each file holds
+    the waveform's samples at a fixed seeded choice of positions (sorted; the same at every run of the same shapes)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = [w.detach().reshape(-1).float().cpu().numpy() for w in waveforms]
+    total = sum(a.nbytes for a in arrs)
+    for i, a in enumerate(arrs):
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.size * (DUMP_LIMIT_BYTES / total)))
+            a = a[np.sort(np.random.default_rng(4242 + i).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(path, f"waveform_{i}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -494,6 +522,11 @@ def main():
     ap.add_argument("--steps", type=int, default=12)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=30.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure per_call, roofline (with its families) and cpu_baseline; "
+                         "a plain run leaves them null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output waveforms to DIR/waveform_<i>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-per-call", action="store_true", help="skip the per-call comparison after a clip stream")
     ap.add_argument("--no-roofline", action="store_true", help="skip the instrumented roofline pass (profiling)")
@@ -619,6 +652,7 @@ def main():
             got = gather_waveforms(outs, dist, dst=0)
             if got is not None:
                 gathered[0] += sum(len(g) for g in got)
+        last_outs[0] = outs
         return outs[-1]
 
     def run_stream(nsteps):
@@ -633,6 +667,7 @@ def main():
                 if dist is not None and got is not None:
                     gathered[0] += len(got)
                 last = got[-1] if got else last
+                last_outs[0] = got or []
             return last
         order = [clips[i % len(clips)] for i in range(nsteps * len(clips))]
         outs = vc.pipeline_device_stream(hub, net_g, 0, order, 0, "v2", 0.33, index, args.index_rate, args.f0,
@@ -641,9 +676,11 @@ def main():
             got = gather_waveforms(outs, dist, dst=0)
             if got is not None:
                 gathered[0] += sum(len(g) for g in got)
+        last_outs[0] = outs[-len(clips):]  # the last step's clips
         return outs[-1]
 
     p2p = {}
+    last_outs = [None]  # the waveforms the last step handed back (--dump-outputs)
 
     gathered = [0]
     if host_visible:  # pinned buffers allocated before the timed region
@@ -673,8 +710,10 @@ def main():
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outs[0] or [])
     per_call = None
-    if args.stream and world == 1 and not args.no_per_call and mine is None:
+    if args.full and args.stream and world == 1 and not args.no_per_call and mine is None:
         # the same K steps as one pipeline_device call per clip, each finished before the next (the
         # reference's loop): the stream's gain over it, measured on the same box right after
         torch.cuda.synchronize()
@@ -694,7 +733,7 @@ def main():
     gathered_per_step = gathered[0] / max(args.warmup + args.steps, 1) if dist is not None else len(clips)
 
     roof = None
-    if rank == 0 and not args.no_roofline and mine is None:
+    if args.full and rank == 0 and not args.no_roofline and mine is None:
         with ConvProbe() as probe:  # one eager pass (a graph replay launches no host-side conv calls)
             # park the GPU first so that the host queues the pass's launches ahead of it: each event pair then
             # brackets its kernel, not the host's issue gap before it (short launches would otherwise count
@@ -760,7 +799,7 @@ def main():
                 # the other kernel families of the same per-call pass, device kernel stamps (torch.profiler)
                 "families": family_rooflines(probe.aux, fam_ms) if fam_ms else None}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
     if rank == 0:
         line = {"metric": METRIC, "value": round(value, 3), "unit": "audio-s/s", "n_gpus": world,

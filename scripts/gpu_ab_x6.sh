@@ -13,6 +13,6 @@ for x in 0 1; do
   tail -12 $O/conv_xcd$x.log
 done
 for x in 0 1; do
-  RVC_X6_XCD=$x RVC_X6_LD4_K=$((3*x)) timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-roofline --steps 10 --warmup 3 > $O/bench$x.log 2>&1 || exit $?
+  RVC_X6_XCD=$x RVC_X6_LD4_K=$((3*x)) timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-roofline --steps 10 --warmup 3 > $O/bench$x.log 2>&1 || exit $?
   echo "bench xcd/ld4 $x: $(grep -o '"value": [0-9.]*' $O/bench$x.log | head -2 | tr '\n' ' ')"
 done

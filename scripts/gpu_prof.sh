@@ -1,5 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel-trace stats of a short bench run; usage: gpu_prof.sh TAG [bench args]
+# (the timed stream alone; pass --full to have the per-call and roofline passes in the trace as well)
 set -u
 TAG=${1:?tag}; shift
 export TMPDIR=/tmp

@@ -112,12 +112,21 @@ struct RbGeom {
 template <int C, int NP>
 constexpr int rb_nr() { return C == 32 && NP == 3 ? 2 : 1; }
 
+// Per-row epilogue constants (F16: the two images' row reciprocal scales; both biases).  They depend only on the wave and
+// lane, so a block fetches them once: 1 row fragment per wave keeps its 4 rows' 16 floats in registers, 2 row fragments
+// (C = 128, WIDE) and the 6-pass pairs (no register room: 168 VGPRs) read a [4][C] float table in LDS (rs1, b1, rs2, b2)
+// filled before the first barrier.  Fetched per tile from global memory they queued in vmcnt behind the weight ring and
+// every epilogue drained it ("Spill reloads and per-tile constant loads").
+template <int C, int NP, bool WIDE = false>
+constexpr bool rb_ctab() { return RbGeom<C, WIDE>::FM == 2 || NP == 6; }
+
 template <int C, int NP, bool WIDE = false>
 size_t rb_lds_bytes(int K, int dil) {
     using G = RbGeom<C, WIDE>;
     constexpr int NPL = NP == 6 ? 3 : (NP == 3 ? 2 : 1);
     const int Wx = G::TW + (K - 1) * dil;
-    return (size_t)G::NCH * (Wx + G::TW) * NPL * 64 + (G::RLDS ? (size_t)rb_nr<C, NP>() * C * G::RSTR * 4 : 0) + 64;  // + scales
+    return (size_t)G::NCH * (Wx + G::TW) * NPL * 64 + (G::RLDS ? (size_t)rb_nr<C, NP>() * C * G::RSTR * 4 : 0) + 64  // + scales
+           + (rb_ctab<C, NP, WIDE>() ? 4 * C * 4 : 0);
 }
 
 // F16 (with NP = 3): split-fp16 operands (x6_common.h split2h).  The loader waves take each staged x tile's
@@ -149,10 +158,13 @@ __global__ __launch_bounds__(768, 1) void resblock_x6_kernel(RbParams p, const f
     auto Rbuf = [&](int k) __attribute__((always_inline)) { return Rs0 + (NR == 2 ? (k & 1) * C * RSTR : 0); };
     float* xmax = Rs0 + (G::RLDS ? NR * C * RSTR : 0);  // F16: [2 tile parities][4 loader waves] x tile |max|
     float* tmaxs = xmax + 8;      // F16: [8 compute waves] T tile |max|
+    constexpr bool CTAB = rb_ctab<C, NP, WIDE>();
+    float* ctab = tmaxs + 8;      // CTAB: [4][C] rs1, b1, rs2, b2
     const int ntc = (L + N - 1) / N;  // time tiles per clip
     const int ntiles = p.B * ntc;
     const int my_n = (int)blockIdx.x < ntiles ? (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // (the wave index as a scalar: the row / column group and everything derived from them stay out of the VGPRs)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (wave == 0) {
         RB_STAMP(248, RB_NOW());
         RB_STAMP(249, (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)));   // HW_ID
@@ -333,10 +345,15 @@ __global__ __launch_bounds__(768, 1) void resblock_x6_kernel(RbParams p, const f
     floatx4 acc[FM][FN];
     // one k-step: B fragments from the LDS image (X for c1 with tap stride d, T for c2), NP passes
     auto compute = [&](const uint4* buf, int tof, int nfrag, const uint4 (&a)[NPL][FM]) __attribute__((always_inline)) {
-        auto bload = [&](int j, uint4 (&bq)[NPL]) __attribute__((always_inline)) {
-            const int pos = (cg * FN + j) * 16 + ln + tof;
+        // the lane's slots for column fragment 0, per k-step; fragment j sits 16 positions on, a constant offset (the
+        // swizzle takes pos & 7 at most) that folds into the read's immediate -- one live register per plane, not one
+        // per fragment and plane
+        int s0[NPL];
 #pragma unroll
-            for (int q = 0; q < NPL; ++q) bq[q] = buf[x_slot<NPL>(pos, q, lg)];
+        for (int q = 0; q < NPL; ++q) s0[q] = x_slot<NPL>(cg * FN * 16 + ln + tof, q, lg);
+        auto bload = [&](int j, uint4 (&bq)[NPL]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < NPL; ++q) bq[q] = buf[s0[q] + j * (16 * 4 * (NPL == 2 ? 2 : NPL))];
         };
         uint4 bb[2][NPL];
         bload(0, bb[0]);
@@ -381,6 +398,42 @@ __global__ __launch_bounds__(768, 1) void resblock_x6_kernel(RbParams p, const f
             if (++l_ch == NCH) { l_ch = 0; l_two = !l_two; }
         }
     };
+    // F16: row reciprocal scales of both images (after each image); the per-row constants once per block, ahead of
+    // the ring's first loads in vmcnt (rb_ctab)
+    float creg[CTAB ? 1 : 4][4];  // !CTAB: rs1, b1, rs2, b2 of this lane's 4 rows
+    {
+        const float* rs1 = reinterpret_cast<const float*>(p.w1x + (int64_t)K * NCH * p.nmf1 * 3 * 64);
+        const float* rs2 = reinterpret_cast<const float*>(p.w2x + (int64_t)K * NCH * p.nmf2 * 3 * 64);
+        if constexpr (CTAB) {
+            if (threadIdx.x < C) {
+                if constexpr (F16) {
+                    ctab[threadIdx.x] = rs1[threadIdx.x];
+                    ctab[2 * C + threadIdx.x] = rs2[threadIdx.x];
+                }
+                ctab[C + threadIdx.x] = p.b1[threadIdx.x];
+                ctab[3 * C + threadIdx.x] = p.b2[threadIdx.x];
+            }
+        } else {
+            const int m0 = rg * 16 + 4 * lg;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                creg[0][r] = F16 ? rs1[m0 + r] : 1.f;
+                creg[1][r] = p.b1[m0 + r];
+                creg[2][r] = F16 ? rs2[m0 + r] : 1.f;
+                creg[3][r] = p.b2[m0 + r];
+            }
+        }
+    }
+    // constant w (0 rs1, 1 b1, 2 rs2, 3 b2) of row fragment i's 4 rows of this lane
+    auto cget = [&](int w, int i, float (&o)[4]) __attribute__((always_inline)) {
+        if constexpr (CTAB) {
+            const float4 v = *reinterpret_cast<const float4*>(ctab + w * C + (rg * FM + i) * 16 + 4 * lg);
+            o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[r] = creg[w][r];
+        }
+    };
 #pragma unroll
     for (int i = 0; i < PD; ++i) {
         aload(l_two, l_ch, l_t, abuf[i]);
@@ -392,9 +445,7 @@ __global__ __launch_bounds__(768, 1) void resblock_x6_kernel(RbParams p, const f
     int n0 = 0;
     float* yb = y_;  // the current tile's clip
     const float* xres = x_;  // C = 128 / WIDE: the current tile's clip of x, the residual
-    // F16: row reciprocal scales of both images (after each image), the x tile's and T tile's reciprocals
-    const float* rs1 = reinterpret_cast<const float*>(p.w1x + (int64_t)K * NCH * p.nmf1 * 3 * 64);
-    const float* rs2 = reinterpret_cast<const float*>(p.w2x + (int64_t)K * NCH * p.nmf2 * 3 * 64);
+    // F16: the T tile's reciprocal scale
     float t_rs = 1.f;
     const bool ylds_c = G::RLDS && F16 && p.ylds;  // block-uniform
     if constexpr (F16) __syncthreads();  // B_pre
@@ -437,14 +488,16 @@ __global__ __launch_bounds__(768, 1) void resblock_x6_kernel(RbParams p, const f
                         float m = 0.f;
 #pragma unroll
                         for (int i = 0; i < FM; ++i) {
-                            const int m0 = (rg * FM + i) * 16 + 4 * lg;
+                            float rs1[4], b1[4];
+                            cget(0, i, rs1);
+                            cget(1, i, b1);
 #pragma unroll
                             for (int j = 0; j < FN; ++j) {
                                 const int q = n0 - hk + (cg * FN + j) * 16 + ln;
                                 const bool ok = q >= 0 && q < L;
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) {
-                                    float v = acc[i][j][r] * (rs1[m0 + r] * x_rs) + p.b1[m0 + r];
+                                    float v = acc[i][j][r] * (rs1[r] * x_rs) + b1[r];
                                     v = v >= 0.f ? v : v * p.slope;
                                     acc[i][j][r] = ok ? v : 0.f;
                                     m = fmaxf(m, fabsf(acc[i][j][r]));
@@ -465,7 +518,8 @@ __global__ __launch_bounds__(768, 1) void resblock_x6_kernel(RbParams p, const f
 #pragma unroll
                     for (int i = 0; i < FM; ++i) {
                         const int mf = rg * FM + i;
-                        const int m0 = mf * 16 + 4 * lg;  // this lane's 4 rows
+                        float b1[4];
+                        if constexpr (!F16) cget(1, i, b1);
                         const int tch = (mf * 16) / 32, tg8 = (mf & 1) * 2 + (lg >> 1), thalf = lg & 1;
                         uint4* tb = Ts + tch * TW * NPL * 4;
 #pragma unroll
@@ -482,7 +536,7 @@ __global__ __launch_bounds__(768, 1) void resblock_x6_kernel(RbParams p, const f
                                     if constexpr (F16) {
                                         v2[e] = acc[i][j][2 * r2 + e] * tsc;
                                     } else {
-                                        float v = acc[i][j][2 * r2 + e] + p.b1[m0 + 2 * r2 + e];
+                                        float v = acc[i][j][2 * r2 + e] + b1[2 * r2 + e];
                                         v = v >= 0.f ? v : v * p.slope;
                                         v2[e] = ok ? v : 0.f;
                                     }
@@ -531,9 +585,12 @@ __global__ __launch_bounds__(768, 1) void resblock_x6_kernel(RbParams p, const f
                                 const int q = n0 + (cg * FN + j) * 16 + ln;
                                 qc[j] = q < L ? q : L - 1;
                             }
+                            float rs2[4], b2[4];
+                            if constexpr (F16) cget(2, i, rs2);
+                            cget(3, i, b2);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                const float f = F16 ? rs2[m0 + r] * t_rs : 1.f, bb = p.b2[m0 + r];
+                                const float f = F16 ? rs2[r] * t_rs : 1.f, bb = b2[r];
 #pragma unroll
                                 for (int j = 0; j < FN; ++j) acc[i][j][r] = (F16 ? acc[i][j][r] * f : acc[i][j][r]) + bb;
                             }
@@ -568,26 +625,70 @@ __global__ __launch_bounds__(768, 1) void resblock_x6_kernel(RbParams p, const f
                             }
                         }
                     } else {
+                        // residual from R: the same loads-first form -- per row fragment every R read (clamped
+                        // columns), then the arithmetic, then every R write (YLDS: the loaders store them) or masked
+                        // store, the block-uniform switches outside the element loops.  Per element (constants and
+                        // accumulate operand from global memory, R read, branch, write) each of a wave's 16 elements
+                        // was a global round trip that also drained the weight ring (rb_stamps r6: 3.5-4.8k cycles
+                        // per tile at C = 32)
+                        float* Rk = Rbuf(k);
 #pragma unroll
-                    for (int i = 0; i < FM; ++i) {
-                        const int m0 = (rg * FM + i) * 16 + 4 * lg;
+                        for (int i = 0; i < FM; ++i) {
+                            const int m0 = (rg * FM + i) * 16 + 4 * lg;
+                            float rs2[4], b2[4];
+                            if constexpr (F16) cget(2, i, rs2);
+                            cget(3, i, b2);
+                            float tmp[FN][4];
 #pragma unroll
-                        for (int j = 0; j < FN; ++j) {
-                            const int col = (cg * FN + j) * 16 + ln;
-                            const int q = n0 + col;
-                            if (cg * FN + j < NF2 && col < N && q < L) {
+                            for (int j = 0; j < FN; ++j) {
+                                const int col = (cg * FN + j) * 16 + ln;
+                                const int cc = col < N ? col : N - 1;
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) tmp[j][r] = Rk[(m0 + r) * RSTR + cc];
+                            }
+#pragma unroll
+                            for (int j = 0; j < FN; ++j)
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) {
-                                    float v = (F16 ? acc[i][j][r] * (rs2[m0 + r] * t_rs) : acc[i][j][r]) + p.b2[m0 + r];
-                                    if constexpr (G::RLDS) v = v + Rbuf(k)[(m0 + r) * RSTR + col];
-                                    else v = v + xres[(int64_t)(m0 + r) * L + q];
-                                    if (p.accumulate) v += YREG ? yold[i][j][r] : yb[(int64_t)(m0 + r) * L + q];
-                                    if (G::RLDS && F16 && ylds_c) Rbuf(k)[(m0 + r) * RSTR + col] = v;  // the loaders store it
-                                    else yb[(int64_t)(m0 + r) * L + q] = v;
+                                    const float v = (F16 ? acc[i][j][r] * (rs2[r] * t_rs) : acc[i][j][r]) + b2[r];
+                                    acc[i][j][r] = v + tmp[j][r];
+                                }
+                            if (p.accumulate) {
+                                if constexpr (!YREG) {
+#pragma unroll
+                                    for (int j = 0; j < FN; ++j) {
+                                        const int q = n0 + (cg * FN + j) * 16 + ln;
+                                        const int qc = q < L ? q : L - 1;
+#pragma unroll
+                                        for (int r = 0; r < 4; ++r) tmp[j][r] = yb[(int64_t)(m0 + r) * L + qc];
+                                    }
+                                }
+#pragma unroll
+                                for (int j = 0; j < FN; ++j)
+#pragma unroll
+                                    for (int r = 0; r < 4; ++r) acc[i][j][r] += YREG ? yold[i][j][r] : tmp[j][r];
+                            }
+                            if (ylds_c) {
+#pragma unroll
+                                for (int j = 0; j < FN; ++j) {
+                                    const int col = (cg * FN + j) * 16 + ln;
+                                    if (cg * FN + j < NF2 && col < N && n0 + col < L) {
+#pragma unroll
+                                        for (int r = 0; r < 4; ++r) Rk[(m0 + r) * RSTR + col] = acc[i][j][r];
+                                    }
+                                }
+                            } else {
+#pragma unroll
+                                for (int j = 0; j < FN; ++j) {
+                                    const int col = (cg * FN + j) * 16 + ln;
+                                    const int q = n0 + col;
+                                    if (cg * FN + j < NF2 && col < N && q < L) {
+#pragma unroll
+                                        for (int r = 0; r < 4; ++r) yb[(int64_t)(m0 + r) * L + q] = acc[i][j][r];
+                                    }
                                 }
                             }
                         }
-                    }
                     }
                     if (RVC_CONV_STAMPS && wave == 0 && k < RB_STAMP_NT) RB_STAMP(8 * k + 5, RB_NOW());
                 }

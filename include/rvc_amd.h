@@ -292,7 +292,14 @@ int rvc_gate(const float* a, float* out, int64_t B, int64_t H, int64_t T, rvc_st
 int rvc_flip_channels(const float* x, float* out, int64_t B, int64_t C, int64_t T, rvc_stream_t stream);
 /* out[b][c][r] = in[b][r][c] */
 int rvc_transpose(const float* in, float* out, int64_t B, int64_t R, int64_t C, rvc_stream_t stream);
-/* standard normal noise, Philox4x32-10 counter stream (seed, offset) */
+/* standard normal noise, Philox4x32-10 counter stream (seed, offset): value e of a call is draw e % 4 of counter
+ * e / 4 + offset.  Counter ranges the synthesizer's draws take under a clip's seed (disjoint for clips below 2^36
+ * values per draw):
+ *   0                      the prior's z noise                                     [inter][T]
+ *   1 << 40                the harmonic source's additive noise                    [L] (Default), [L][H] (MRF, RefineGAN)
+ *   1 << 39                the harmonic source's initial phases (rvc_rand_uniform)  [H] (MRF, RefineGAN)
+ *   (2 + k) << 40          RefineGAN's k-th AdaIN draw, k = 0 .. 6 * stages - 1 in the reference's draw order
+ *                          (stage-major, then branch, then the leading and the trailing AdaIN) */
 int rvc_randn(float* out, int64_t n, uint64_t seed, uint64_t offset, rvc_stream_t stream);
 /* the same with seed += *seed_add read on the device (seed_add may be NULL): graph replays draw fresh noise */
 int rvc_randn_ex(float* out, int64_t n, uint64_t seed, uint64_t offset, const uint64_t* seed_add,
@@ -305,6 +312,46 @@ int rvc_rand_triang(float* out, int64_t n, float lo, float hi, uint64_t seed, ui
  * f0 [B][T] -> har [B][T*upp]; noise [B][T*upp]; work: [B][T] floats scratch */
 int rvc_sine_source(const float* f0, const float* noise, float* har, float* work, int64_t B, int64_t T, int upp,
                     float sr, float lin_w, float lin_b, rvc_stream_t stream);
+
+/* ------------------------------------------------------------------ MRF-HiFi-GAN / RefineGAN decoders (vocoder.hip)
+ * Every call takes B clips of one length; clip b's result does not depend on the other clips. */
+#define RVC_HARMONIC_MAX 16 /* harmonics per source */
+#define RVC_ADAIN_BMAX 16   /* clips per rvc_adain call that draws its noise in the kernel */
+/* uniform draws on [0, 1) (24 bits), the Philox counter stream of rvc_randn */
+int rvc_rand_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, const uint64_t* seed_add,
+                     rvc_stream_t stream);
+/* Per-sample harmonic source: SineGenerator + merge    mrf_hifigan.py:45-94 (H = 9, nearest f0, bias),
+ * refinegan.py:66-107 (H = 1, linear f0, lin_b = 0).
+ *   f0 [B][T] -> har [B][L], L = T*upp;  phase0 [B][H] (harmonic 0's is used as given: pass 0 as the reference does);
+ *   noise [B][L][H] (h contiguous);  lin_w: H HOST floats (the merge's weight row), lin_b its bias;
+ *   linear: 0 = nearest f0 upsampling (torch's legacy rule, floorf(i * f32(1/upp))), 1 = linear (align_corners=False).
+ * The phase of harmonic h is the prefix sum over all L samples of the f32 increments ((f0*(h+1))/sr) % 1, accumulated
+ * in f64 with the fractional part taken before sinf (what torch's CPU cumsum computes, up to the wraps it subtracts);
+ * a multi-block scan: block sums, a carry pass, then the per-sample pass.
+ * ws: rvc_harmonic_source_ws_bytes(B, T, upp, H) bytes, 8-byte aligned (-1: bad shape).  Limits: 1 <= H <=
+ * RVC_HARMONIC_MAX, B <= 65535, and L <= 2^24 with linear = 1 (sample indices pass through f32 as in torch).
+ * rvc_harmonic_source_chunk(): samples per block of the scan. */
+int64_t rvc_harmonic_source_ws_bytes(int64_t B, int64_t T, int upp, int H);
+int64_t rvc_harmonic_source_chunk(void);
+int rvc_harmonic_source(const float* f0, const float* phase0, const float* noise, float* har, int64_t B, int64_t T,
+                        int upp, int H, int linear, float sr, const float* lin_w, float lin_b, void* ws,
+                        int64_t ws_bytes, rvc_stream_t stream);
+/* y[b][c][j] = linear interpolation of act(x[b][c][.]) by the integer rate r, j < Lin*r    nn.Upsample(scale_factor=r,
+ * mode="linear"), align_corners=False: source position (j + 0.5)/r - 0.5 clamped at 0, right neighbour clamped at Lin-1,
+ * in the operation order of torch's CPU kernel.  act: RVC_ACT_NONE or RVC_ACT_LRELU(slope), applied to the INPUT samples.
+ * x rows [Lin] contiguous, batch stride x_bstride (0 = C*Lin); y rows [Lin*r] contiguous, batch stride y_bstride
+ * (0 = C*Lin*r; larger to write the first C channels of a wider buffer, whose other rows are left alone).
+ * Limits: B, C <= 65535, Lin*r <= 2^24, x != y. */
+int rvc_upsample_linear(const float* x, float* y, int64_t B, int64_t C, int64_t Lin, int r, int64_t x_bstride,
+                        int64_t y_bstride, int act, float slope, rvc_stream_t stream);
+/* AdaIN: y = out_scale * lrelu(x + n * w[c], slope), or y += that with accumulate    refinegan.py:39-46
+ *   x, y [B][C][L] contiguous (y may be x unless accumulate), w [C].
+ *   noise [B][C][L], or NULL: n is drawn in the kernel, bit-identical to rvc_randn_ex(buf_b, C*L, seeds[b], offset,
+ *   seed_add) filling clip b's buffer; seeds: B HOST values, B <= RVC_ADAIN_BMAX.
+ * The three branches' trailing AdaINs form their mean with accumulate and out_scale = 1/3. */
+int rvc_adain(const float* x, const float* noise, const float* w, float* y, int64_t B, int64_t C, int64_t L,
+              float slope, float out_scale, int accumulate, const uint64_t* seeds, uint64_t offset,
+              const uint64_t* seed_add, rvc_stream_t stream);
 
 /* ------------------------------------------------------------------ RMVPE (RMVPE.py)
  * framesT[n][f] = x[reflect(f*hop + n - nfft/2)] * win[n]               RMVPE.py:168 (torch.stft center)

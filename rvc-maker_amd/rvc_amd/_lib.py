@@ -178,6 +178,15 @@ SIGNATURES = {
     "rvc_rand_triang": [c_void_p, c_int64, c_float, c_float, c_uint64, c_uint64, c_void_p, c_void_p],
     "rvc_sine_source": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_float, c_float,
                         c_void_p],
+    "rvc_rand_uniform": [c_void_p, c_int64, c_uint64, c_uint64, c_void_p, c_void_p],
+    "rvc_harmonic_source_ws_bytes": [c_int64, c_int64, c_int, c_int],
+    "rvc_harmonic_source_chunk": [],
+    "rvc_harmonic_source": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_float,
+                            POINTER(c_float), c_float, c_void_p, c_int64, c_void_p],
+    "rvc_upsample_linear": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_float,
+                            c_void_p],
+    "rvc_adain": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float, c_int,
+                  POINTER(c_uint64), c_uint64, c_void_p, c_void_p],
     "rvc_stft_frames": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p],
     "rvc_spec_mag": [c_void_p, c_void_p, c_int64, c_int64, c_void_p],
     "rvc_stft_mag": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_int64, c_void_p],
@@ -276,7 +285,8 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_contentvec_frames": c_int64, "rvc_rmvpe_frames": c_int64, "rvc_rmvpe_salience_ld": c_int64,
              "rvc_vc_out_len": c_int64, "rvc_device_bytes_in_use": c_int64,
              "rvc_quiet_points_count": c_int64, "rvc_f0_file_resample": c_int64, "rvc_quiet_points_ws_bytes": c_int64,
-             "rvc_fe0_ws_bytes": c_int64}
+             "rvc_fe0_ws_bytes": c_int64, "rvc_harmonic_source_ws_bytes": c_int64,
+             "rvc_harmonic_source_chunk": c_int64}
 
 _lib = None
 

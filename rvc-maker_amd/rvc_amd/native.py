@@ -120,6 +120,11 @@ class NativeSynth(_Ctx):
     library) or any dict of already-folded fp32 tensors (synth.fold_weight_norm)."""
 
     def __init__(self, cpt: dict, device: str = "cuda", weights: dict | None = None, precision: str = "fp32"):
+        vocoder = cpt.get("vocoder", "Default")
+        if vocoder != "Default":  # before the library is touched: rvc_load_synth would fail on a missing tensor
+            raise NotImplementedError(f"NativeSynth: vocoder {vocoder!r} is not in the model-level C API "
+                                      "(rvc_load_synth loads the Default NSF-HiFiGAN decoder); use SynthesizerAMD, "
+                                      "or the op-level entry points from a non-Python host")
         super().__init__(device, precision)
         self.cfg = synth_cfg(cpt)
         self.upp = int(np.prod(cpt["config"][12]))

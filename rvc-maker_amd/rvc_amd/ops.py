@@ -573,6 +573,92 @@ def sine_source(f0, noise, har, work, B, T, upp, sr, lin_w, lin_b):
     return har
 
 
+# ------------------------------------------------------------------ MRF-HiFi-GAN / RefineGAN (vocoder.hip)
+# Philox counter ranges of the extra draws under a clip's seed (include/rvc_amd.h, next to rvc_randn)
+OFF_SINE = 1 << 40
+OFF_PHASE = 1 << 39
+ADAIN_BMAX = 16  # RVC_ADAIN_BMAX
+
+
+def off_adain(k: int) -> int:
+    """Counter offset of RefineGAN's k-th AdaIN draw (the reference's draw order)."""
+    return (2 + k) << 40
+
+
+def rand_uniform(out, seed, offset=0):
+    """Uniform draws on [0, 1) (Philox counter stream; device seed added when set)."""
+    add = _p(_DEV_SEED) if _DEV_SEED is not None else None
+    check(_lib.load().rvc_rand_uniform(_p(out), out.numel(), seed, offset, add, _stream()), "rand_uniform")
+    return out
+
+
+def harmonic_source(f0, phase0, noise, har, B, T, upp, H, sr, lin_w, lin_b=0.0, linear=False):
+    """The per-sample harmonic source (rvc_harmonic_source): f0 [B][T], phase0 [B][H], noise [B][T*upp][H] ->
+    har [B][T*upp]; lin_w: the merge's H weights (host floats), lin_b its bias."""
+    L = T * upp
+    lin_w = [float(v) for v in lin_w]
+    if len(lin_w) != H:
+        raise ValueError("harmonic_source: one merge weight per harmonic")
+    if f0.numel() < B * T or phase0.numel() < B * H or noise.numel() < B * L * H or har.numel() < B * L:
+        raise ValueError("harmonic_source: size mismatch")
+    for t in (f0, phase0, noise, har):
+        if not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError("harmonic_source: contiguous f32 tensors")
+    lib = _lib.load()
+    need = lib.rvc_harmonic_source_ws_bytes(B, T, upp, H)
+    if need < 0:
+        raise ValueError(f"harmonic_source: unsupported shape B={B} T={T} upp={upp} H={H}")
+    ws = _workspace(har.device, need, "hsrc")
+    check(lib.rvc_harmonic_source(_p(f0), _p(phase0), _p(noise), _p(har), B, T, upp, H, int(bool(linear)), float(sr),
+                                  (ctypes.c_float * H)(*lin_w), float(lin_b), _p(ws), need, _stream()),
+          "harmonic_source")
+    return har
+
+
+def upsample_linear(x, r, out=None, act=ACT_NONE, slope=0.0, y_bstride=0):
+    """nn.Upsample(scale_factor=r, mode="linear") of act(x), x [B][C][Lin] contiguous -> [B][C][Lin*r] (or the first C
+    channels of ``out``, a wider [B][C'][Lin*r] buffer with batch stride ``y_bstride``)."""
+    B, C, Lin = _shape3(x)
+    Lout = Lin * r
+    if not x.is_contiguous() or x.dtype != torch.float32:
+        raise ValueError("upsample_linear: contiguous f32 input")
+    if out is None:
+        out = torch.empty(B, C, Lout, device=x.device)
+    elif out.dtype != torch.float32 or _room(out) < (B - 1) * (y_bstride or C * Lout) + C * Lout or \
+            (y_bstride and y_bstride < C * Lout):
+        raise ValueError("upsample_linear: output buffer too small")
+    check(_lib.load().rvc_upsample_linear(_p(x), _p(out), B, C, Lin, r, 0, y_bstride, act, slope, _stream()),
+          "upsample_linear")
+    return out
+
+
+def adain(x, w, out, noise=None, seeds=None, offset=0, slope=0.2, out_scale=1.0, accumulate=False):
+    """out (+)= out_scale * lrelu(x + n * w[c], slope) over x [B][C][L] (rvc_adain); n from ``noise`` [B][C][L], or
+    drawn in the kernel exactly as ``randn(buf[b], seeds[b], offset)`` would fill it."""
+    B, C, L = _shape3(x)
+    if out.numel() < B * C * L or w.numel() < C or not x.is_contiguous() or not out.is_contiguous() or \
+            x.dtype != torch.float32 or out.dtype != torch.float32:
+        raise ValueError("adain: size mismatch")
+    lib = _lib.load()
+    if noise is not None:
+        if noise.numel() < B * C * L or not noise.is_contiguous():
+            raise ValueError("adain: noise [B][C][L]")
+        check(lib.rvc_adain(_p(x), _p(noise), _p(w), _p(out), B, C, L, slope, out_scale, int(bool(accumulate)), None,
+                            0, None, _stream()), "adain")
+        return out
+    if seeds is None or len(seeds) != B:
+        raise ValueError("adain: one seed per clip")
+    add = _p(_DEV_SEED) if _DEV_SEED is not None else None
+    n = C * L
+    for b0 in range(0, B, ADAIN_BMAX):
+        nb = min(ADAIN_BMAX, B - b0)
+        sd = (ctypes.c_uint64 * nb)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds[b0:b0 + nb]])
+        xs, ys = x.reshape(-1)[b0 * n:], out.reshape(-1)[b0 * n:]
+        check(lib.rvc_adain(_p(xs), None, _p(w), _p(ys), nb, C, L, slope, out_scale, int(bool(accumulate)), sd,
+                            offset, add, _stream()), "adain")
+    return out
+
+
 def stft_frames(x, win, out, N, F, nfft, hop):
     if x.numel() < N or win.numel() < nfft or out.numel() < nfft * F:
         raise ValueError("stft_frames: size mismatch")

@@ -112,7 +112,9 @@ class VC:
         self._finalizer = weakref.finalize(self, _close_streams, self._owned)
         self.embed_suffix = None  # pipeline()'s embed_suffix during that call (convert.py:390); None = the model's own
         self.crepe = dict(crepe or {})  # capacity -> CrepeAMD (loaded on first use otherwise)
-        self.noise_fn = None  # parity hook: noise_fn(seg, "z"|"sine", shape) -> device tensor
+        # parity hook: noise_fn(seg, kind, shape) -> device tensor; kind "z" | "sine", and for the MRF-HiFi-GAN and
+        # RefineGAN decoders also "phase" (the source's initial phases, uniform) and "adain<k>" (_decoder_noise)
+        self.noise_fn = None
         self.seed = 0
         self._ws = None
         self.filt = ops.FiltFilt(BH, AH)
@@ -207,6 +209,25 @@ class VC:
         z, _, _, gc = net_g.prior_cf(phone, pitch.contiguous(), sid, zn, seed)
         return {"z": z, "gc": gc, "pitchf": pitchf.contiguous(), "T": T}
 
+    def _decoder_noise(self, net_g, segs, T):
+        """decode_batch's parity draws from noise_fn for the segments ``segs`` (one per clip): the sine noise
+        (1, L, 1) as ever -- (1, L, H) for a decoder with H harmonics -- and, for the MRF-HiFi-GAN and RefineGAN
+        decoders, "phase" (1, H) and RefineGAN's "adain<k>" (1, C, L) in draw order.  {} without a noise_fn."""
+        if not self.noise_fn:
+            return {}
+        H = getattr(net_g, "n_harm", 1)
+        L = T * net_g.upp
+        kw = {"sine_noise": torch.stack([self.noise_fn(g, "sine", (1, L, H)).reshape(L, H) for g in segs])}
+        if getattr(net_g, "kind", "nsf") == "nsf":
+            kw["sine_noise"] = kw["sine_noise"].reshape(len(segs), L)
+            return kw
+        kw["phase0"] = torch.stack([self.noise_fn(g, "phase", (1, H)).reshape(H) for g in segs])
+        shapes = net_g.adain_shapes(T)
+        if shapes:
+            kw["adain_noise"] = [torch.stack([self.noise_fn(g, f"adain{k}", (1, C, Lk)).reshape(C, Lk) for g in segs])
+                                 for k, (C, Lk) in enumerate(shapes)]
+        return kw
+
     def voice_conversion_batch_device(self, model, net_g, sid, items, version, protect, index=None, index_rate=0.0,
                                       seeds=(), noise_segs=None):
         """``voice_conversion_device`` over B clips of one length with the synthesizer batched: retrieval and
@@ -238,18 +259,17 @@ class VC:
             pitch[b].copy_(coarse[:T])
             pf[b].copy_(pitchf[:T])
         T = phone.shape[2]
-        zn = sn = None
+        zn = None
+        segs = noise_segs or [0] * B
         if self.noise_fn:
-            segs = noise_segs or [0] * B
             zn = torch.stack([self.noise_fn(g, "z", (1, net_g.inter, T)).reshape(net_g.inter, T) for g in segs])
-            sn = torch.stack([self.noise_fn(g, "sine", (1, T * net_g.upp, 1)).reshape(-1) for g in segs])
         z, _, _, gc = net_g.prior_batch(phone, pitch, sid, zn, seeds)
-        return net_g.decode_batch(z, pf, gc, sn, seeds)
+        return net_g.decode_batch(z, pf, gc, seeds=seeds, **self._decoder_noise(net_g, segs, T))
 
     def generate_device(self, net_g, prep, seg, seed):
         """The NSF generator on prior_device's z (synthesizers.py:461-465) -> waveform [T*upp]."""
-        sn = self.noise_fn(seg, "sine", (1, prep["T"] * net_g.upp, 1)) if self.noise_fn else None
-        return net_g.decode_cf(prep["z"], prep["pitchf"], prep["gc"], sn, seed)
+        return net_g.decode_cf(prep["z"], prep["pitchf"], prep["gc"], seed=seed,
+                               **self._decoder_noise(net_g, [seg], prep["T"]))
 
     def pipeline_device(self, model, net_g, sid, audio, pitch, version, protect, index=None, index_rate=0.0,
                         f0_method="rmvpe", f0_autotune=False, f0_autotune_strength=1.0, inp_f0=None,

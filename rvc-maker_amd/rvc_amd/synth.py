@@ -12,6 +12,11 @@ All compute runs in librvc_amd.so kernels on the current torch stream:
                its epilogue) + 3 ResBlocks (lrelu fused, residual / running sum
                fused in the epilogue; at 32 / 64 channels each conv pair is one fused launch,
                csrc/resblock.hip)], conv_post (lrelu 0.01 + tanh fused)
+  MRF-HiFi-GAN (vocoder "MRF-HiFi-GAN" / "MRF HiFi-GAN") the NSF generator's launches on the MRF weights, after the
+               per-sample 9-harmonic source (harmonic_source, csrc/vocoder.hip)
+  RefineGAN    (vocoder "RefineGAN") harmonic_source (1 harmonic, linear f0), mel_conv(+cond) and the folded pre_conv,
+               4 x [upsample_linear (lrelu 0.2 on its input) + downsample conv into one buffer, input_conv,
+               3 x (adain, 3 ResBlock pairs, adain accumulating the branches' mean)], conv_post (lrelu 0.2 + tanh)
 
 Only full-length phones are supported (x_mask all ones): in ``VC.voice_conversion``
 ``p_len == phone length`` always holds (2*T_f <= N//160; see DESIGN.md).
@@ -28,6 +33,8 @@ from .ops import ACT_LRELU, ACT_RELU, ACT_TANH, Conv, ConvT
 import os
 
 LRELU_SLOPE = 0.1
+REFINEGAN_SLOPE = 0.2  # refinegan.py:110
+MRF_NAMES = ("MRF-HiFi-GAN", "MRF HiFi-GAN")  # both spellings synthesizers.py:420 accepts
 # the generator's |max| side channel (RVC_AMD_AMAX=0: per-tile pre-passes, the round-4 form; rvc_model.cpp reads the
 # same switch): cells per upsample stage -- y, then each unfused pair's c1 output and non-last c2 output
 AMAX = os.environ.get("RVC_AMD_AMAX", "1") != "0"
@@ -73,8 +80,20 @@ class SynthesizerAMD:
         (_, _, self.inter, self.hidden, self.filt, self.n_heads, self.n_layers, self.ksz, _, _, self.rks, self.rds,
          self.ur, self.uic, self.uks, self.spk, self.gin, self.sr) = cfg
         self.version = cpt.get("version", "v1")
-        if cpt.get("f0", 1) != 1 or cpt.get("vocoder", "Default") != "Default":
-            raise NotImplementedError("rvc_amd: only NSF-HiFiGAN (f0=1, vocoder Default) models are on the hot path")
+        self.vocoder = cpt.get("vocoder", "Default")
+        if cpt.get("f0", 1) != 1:
+            raise NotImplementedError("rvc_amd: only f0 models are on the hot path (the reference's no-f0 Generator "
+                                      "does not run)")
+        # the decoder by the checkpoint's vocoder field, as synthesizers.py:418-421 picks it
+        if self.vocoder == "RefineGAN":
+            self.kind = "refinegan"
+        elif self.vocoder in MRF_NAMES:
+            self.kind = "mrf"
+        elif self.vocoder == "Default":
+            self.kind = "nsf"
+        else:
+            raise NotImplementedError(f"rvc_amd: vocoder {self.vocoder!r}: Default, MRF-HiFi-GAN and RefineGAN are "
+                                      "on the hot path")
         self.upp = math.prod(self.ur)
         self.device = device
         W = fold_weight_norm(cpt["weight"])
@@ -124,29 +143,103 @@ class SynthesizerAMD:
                     F["rs_b"].append(Conv(rw, rb, device=dev))
             self.flows.append(F)
         # ---- generator
-        self.lin_w = float(W["dec.m_source.l_linear.weight"].reshape(-1)[0])
+        if self.kind == "refinegan":
+            self._load_refinegan(W, dev)
+            return
+        mrf = self.kind == "mrf"
+        if mrf:  # SourceModuleHnNSF(harmonic_num=8): Linear(9, 1) (mrf_hifigan.py:84-94)
+            self.n_harm = int(W["dec.m_source.l_linear.weight"].numel())
+            self.src_w = [float(v) for v in W["dec.m_source.l_linear.weight"].reshape(-1)]
+            self.src_linear = False
+        else:
+            self.n_harm = 1
+            self.lin_w = float(W["dec.m_source.l_linear.weight"].reshape(-1)[0])
         self.lin_b = float(W["dec.m_source.l_linear.bias"].reshape(-1)[0])
         self.conv_pre = Conv(W["dec.conv_pre.weight"], W["dec.conv_pre.bias"], device=dev)
         nup = len(self.ur)
         self.chans = [self.uic // (2 ** (i + 1)) for i in range(nup)]
         strides = [math.prod(self.ur[i + 1:]) if i + 1 < nup else 1 for i in range(nup)]
         self.ups, self.noise, self.res = [], [], []
+        ups_name = "dec.upsamples" if mrf else "dec.ups"
         for i, (u, k) in enumerate(zip(self.ur, self.uks)):
             if u % 2:
                 raise NotImplementedError("odd upsample rates (output_padding) are not used by any shipped config")
-            self.ups.append(ConvT(W[f"dec.ups.{i}.weight"], W[f"dec.ups.{i}.bias"], u, (k - u) // 2, device=dev))
+            self.ups.append(ConvT(W[f"{ups_name}.{i}.weight"], W[f"{ups_name}.{i}.bias"], u, (k - u) // 2, device=dev))
             s = strides[i]
             kn = 1 if s == 1 else s * 2 - s % 2
             self.noise.append((Conv(W[f"dec.noise_convs.{i}.weight"], W[f"dec.noise_convs.{i}.bias"], device=dev), s,
                                0 if s == 1 else (kn - s) // 2))
             blocks = []
             for j, (kk, ds) in enumerate(zip(self.rks, self.rds)):
-                rb = f"dec.resblocks.{i * len(self.rks) + j}."
-                blocks.append((kk, [(d, Conv(W[rb + f"convs1.{m}.weight"], W[rb + f"convs1.{m}.bias"], device=dev),
-                                     Conv(W[rb + f"convs2.{m}.weight"], W[rb + f"convs2.{m}.bias"], device=dev))
-                                    for m, d in enumerate(ds)]))
+                if mrf:  # MRFLayer = one ResBlock pair (mrf_hifigan.py:14-21)
+                    rb = f"dec.mrfs.{i}.{j}.layers."
+                    names = [(rb + f"{m}.conv1", rb + f"{m}.conv2") for m in range(len(ds))]
+                else:
+                    rb = f"dec.resblocks.{i * len(self.rks) + j}."
+                    names = [(rb + f"convs1.{m}", rb + f"convs2.{m}") for m in range(len(ds))]
+                blocks.append((kk, [(d, Conv(W[n1 + ".weight"], W[n1 + ".bias"], device=dev),
+                                     Conv(W[n2 + ".weight"], W[n2 + ".bias"], device=dev))
+                                    for d, (n1, n2) in zip(ds, names)]))
             self.res.append(blocks)
+        # MRF's conv_post is weight-normed and has a bias (mrf_hifigan.py:119); the NSF generator's has neither
+        self.conv_post = Conv(W["dec.conv_post.weight"], W.get("dec.conv_post.bias") if mrf else None, device=dev)
+
+    def _load_refinegan(self, W, dev):
+        """RefineGANGenerator's tensors (refinegan.py:109-144).  ``upsample_initial_channel`` is 512 whatever the config
+        says; the config's upsample kernel sizes and resblock lists are not read."""
+        if self.upp % 2 or self.upp < 8:
+            # pre_conv + the linear interpolation down to T frames fold into one strided conv only when both
+            # interpolation weights are 1/2, i.e. for an even upp (every shipped config)
+            raise NotImplementedError("RefineGAN with an odd (or < 8) total upsample rate is not on the hot path")
+        self.n_harm, self.src_linear = 1, True
+        self.src_w = [float(W["dec.m_source.merge.0.weight"].reshape(-1)[0])]
+        self.lin_b = 0.0
+        ch = 512
+        # x = interpolate(pre_conv(har), size=T, mode="linear") (refinegan.py:148): frame t reads the full-rate
+        # positions upp*t + upp/2 - 1 and + upp/2 with weight 1/2 each, so it is one 8-tap conv of stride upp on har,
+        # w'[k] = (w[k] + w[k-1]) / 2, starting at sample upp/2 - 4 of each clip -- [256][L] is never materialised
+        w = W["dec.pre_conv.weight"]
+        wf = torch.zeros(w.shape[0], 1, 8)
+        wf[:, :, :7] += 0.5 * w
+        wf[:, :, 1:] += 0.5 * w
+        self.pre_fold = Conv(wf, W["dec.pre_conv.bias"], device=dev)
+        self.pre_off = self.upp // 2 - 4
+        self.mel_conv = Conv(W["dec.mel_conv.weight"], W["dec.mel_conv.bias"], device=dev)
+        nup = len(self.ur)
+        strides = [math.prod(self.ur[i + 1:]) if i + 1 < nup else 1 for i in range(nup)]
+        self.rg_stages = []
+        c = ch
+        for i, u in enumerate(self.ur):
+            s = strides[i]
+            kn = 1 if s == 1 else s * 2 - s % 2
+            p = f"dec.upsample_conv_blocks.{i}."
+            new = c // 2
+            st = dict(rate=u, cin=c, cout=new, down_stride=s, down_pad=0 if s == 1 else (kn - s) // 2,
+                      down=Conv(W[f"dec.downsample_blocks.{i}.weight"], W[f"dec.downsample_blocks.{i}.bias"],
+                                device=dev),
+                      input_conv=Conv(W[p + "input_conv.weight"], W[p + "input_conv.bias"], device=dev), branches=[])
+            if st["down"].Co != c // 4 or st["input_conv"].Ci != c + c // 4:
+                raise ValueError("RefineGAN checkpoint does not have the reference's channel plan")
+            for j, kk in enumerate((3, 7, 11)):
+                rb = p + f"blocks.{j}.1."
+                pairs = [(d, Conv(W[rb + f"convs1.{m}.weight"], W[rb + f"convs1.{m}.bias"], device=dev),
+                          Conv(W[rb + f"convs2.{m}.weight"], W[rb + f"convs2.{m}.bias"], device=dev))
+                         for m, d in enumerate((1, 3, 5))]
+                st["branches"].append((kk, W[p + f"blocks.{j}.0.weight"].contiguous().to(dev), pairs,
+                                       W[p + f"blocks.{j}.2.weight"].contiguous().to(dev)))
+            self.rg_stages.append(st)
+            c = new
         self.conv_post = Conv(W["dec.conv_post.weight"], None, device=dev)
+
+    def adain_shapes(self, T):
+        """(C, L) of RefineGAN's AdaIN draws for T frames, in the reference's draw order (empty for the others)."""
+        if self.kind != "refinegan":
+            return []
+        out, Lc = [], T
+        for st in self.rg_stages:
+            Lc *= st["rate"]
+            out += [(st["cout"], Lc)] * 6
+        return out
 
     # ------------------------------------------------------------------ stages (B clips of one length T:
     # every launch takes the clip batch; B = 1 issues exactly the single-clip launches)
@@ -232,13 +325,24 @@ class SynthesizerAMD:
             x = xf
         return x
 
-    def generator(self, z, nsff0, gdec, T, sine_noise, B=1):
-        """GeneratorNSF.forward (synthesizers.py:144-161) on z [B][inter][T] -> [B][1][T*upp]."""
+    def harmonic_source(self, nsff0, sine_noise, phase0, T, B=1):
+        """The MRF / RefineGAN source module (mrf_hifigan.py:45-94, refinegan.py:66-107): f0 [B][T], noise
+        [B][L][H], initial phases [B][H] (harmonic 0's already zero) -> har [B][L]."""
+        har = torch.empty(B, T * self.upp, device=nsff0.device)
+        return ops.harmonic_source(nsff0, phase0, sine_noise, har, B, T, self.upp, self.n_harm, float(self.sr),
+                                   self.src_w, self.lin_b, linear=self.src_linear)
+
+    def generator(self, z, nsff0, gdec, T, sine_noise, B=1, phase0=None):
+        """GeneratorNSF.forward (synthesizers.py:144-161) on z [B][inter][T] -> [B][1][T*upp]; with the MRF weights
+        HiFiGANMRFGenerator.forward (mrf_hifigan.py:122-139): the same launches after its own source module."""
         dev = z.device
         L = T * self.upp
-        har = torch.empty(B, L, device=dev)
-        work = torch.empty(B, T, device=dev)
-        ops.sine_source(nsff0, sine_noise, har, work, B, T, self.upp, float(self.sr), self.lin_w, self.lin_b)
+        if self.kind == "mrf":
+            har = self.harmonic_source(nsff0, sine_noise, phase0, T, B)
+        else:
+            har = torch.empty(B, L, device=dev)
+            work = torch.empty(B, T, device=dev)
+            ops.sine_source(nsff0, sine_noise, har, work, B, T, self.upp, float(self.sr), self.lin_w, self.lin_b)
         nst = len(self.ur)
         cells = ops.AmaxSlots(AMAX_PER_STAGE * nst + nst + 1, dev, B) if AMAX else None
         # cells after the stages' own: one per stage for its output xs (published by the last resblock's last c2 when
@@ -314,6 +418,61 @@ class SynthesizerAMD:
             scale = 1.0 / nk
         return self.conv_post(x, pad=3, in_act=ACT_LRELU, in_slope=0.01, in_scale=scale, out_act=ACT_TANH)
 
+    def generator_refinegan(self, z, nsff0, gdec, T, sine_noise, phase0, B=1, adain_noise=None, seeds=(0,)):
+        """RefineGANGenerator.forward (refinegan.py:146-159) on z [B][inter][T] -> [B][1][T*upp].  adain_noise: the
+        6 * stages AdaIN draws [B][C][L] in the reference's order (parity), or None: drawn in the AdaIN kernels from
+        seeds[b] at counter offset ops.off_adain(k).  Every conv here reads the output of an elementwise kernel that
+        publishes no |max| cell, so each takes the per-tile pre-pass form (amax_in=None)."""
+        dev = z.device
+        L = T * self.upp
+        slope = REFINEGAN_SLOPE
+        har = self.harmonic_source(nsff0, sine_noise, phase0, T, B)
+        c0 = self.mel_conv.Co + self.pre_fold.Co
+        x = torch.empty(B, c0, T, device=dev)
+        # mel_conv(z) + cond(g) -> channels [0, 256); the folded pre_conv + downward interpolation -> [256, 512)
+        self.mel_conv(z.reshape(B, self.inter, T), pad=3, bias2=gdec, out=x, y_bstride=c0 * T)
+        # the conv engine stages (tile - 1) * stride + K inputs per tile, which a stride of upp does not fit: the 8
+        # samples each frame reads are gathered first ([B][T][8], one strided copy), then the conv runs at stride 8
+        taps = har.view(B, T, self.upp)[:, :, self.pre_off:self.pre_off + 8].contiguous()
+        self.pre_fold(taps.view(B, 1, T * 8), Lout=T, stride=8, out=x[:, self.mel_conv.Co:], y_bstride=c0 * T)
+        Lc, k = T, 0
+        for st in self.rg_stages:
+            r, cin, C = st["rate"], st["cin"], st["cout"]
+            Lo = Lc * r
+            ccat = cin + cin // 4
+            cat = torch.empty(B, ccat, Lo, device=dev)
+            # lrelu, then the linear upsample into the first cin channels; downsample_blocks[i](har) into the rest
+            ops.upsample_linear(x, r, out=cat, act=ACT_LRELU, slope=slope, y_bstride=ccat * Lo)
+            st["down"](har.view(B, 1, L), Lout=Lo, stride=st["down_stride"], pad=st["down_pad"], out=cat[:, cin:],
+                       y_bstride=ccat * Lo)
+            xin = st["input_conv"](cat, pad=3).view(B, C, Lo)
+            del cat
+            xa = torch.empty(B, C, Lo, device=dev)
+            xb = torch.empty(B, C, Lo, device=dev)
+            xs = torch.empty(B, C, Lo, device=dev)
+            t1 = None
+            for j, (kk, w_in, pairs, w_out) in enumerate(st["branches"]):
+                cur = xa
+                ops.adain(xin, w_in, cur, noise=None if adain_noise is None else adain_noise[k], seeds=seeds,
+                          offset=ops.off_adain(k), slope=slope)
+                for d, c1, c2 in pairs:
+                    nxt = xb if cur is xa else xa
+                    if ops.resblock_fusable(c1, c2, d):
+                        ops.resblock_pair(cur, nxt, c1, c2, d, slope)
+                    else:
+                        if t1 is None:
+                            t1 = torch.empty(B, C, Lo, device=dev)
+                        c1(cur, pad=(kk * d - d) // 2, dil=d, out=t1, in_act=ACT_LRELU, in_slope=slope)
+                        c2(t1, pad=(kk - 1) // 2, out=nxt, res=cur, in_act=ACT_LRELU, in_slope=slope)
+                    cur = nxt
+                # the branches' mean: the trailing AdaINs accumulate a third each
+                ops.adain(cur, w_out, xs, noise=None if adain_noise is None else adain_noise[k + 1], seeds=seeds,
+                          offset=ops.off_adain(k + 1), slope=slope, out_scale=1.0 / 3.0, accumulate=j > 0)
+                k += 2
+            del xin, xa, xb, t1
+            x, Lc = xs, Lo
+        return self.conv_post(x, pad=3, in_act=ACT_LRELU, in_slope=slope, out_act=ACT_TANH)
+
     # ------------------------------------------------------------------ public API
     def speaker_cond(self, sid: int):
         g = self.emb_g[sid].view(self.gin, 1)
@@ -340,9 +499,59 @@ class SynthesizerAMD:
         z = self.flow_reverse(z_p, gc, T, B)
         return z, z_p, stats, gc
 
-    def decode_batch(self, z, nsff0, gc, sine_noise=None, seeds=(0,)):
-        """The NSF generator on z [B][inter][T] (synthesizers.py:461-465) -> o [B][T*upp]; clip b's sine
-        noise from seeds[b]."""
+    def _decode_vocoder(self, z, nsff0, gc, sine_noise, seeds, phase0, adain_noise):
+        """decode_batch for the MRF-HiFi-GAN and RefineGAN decoders: the source's draws (noise [B][L][H] at counter
+        offset ops.OFF_SINE, initial phases [B][H] at ops.OFF_PHASE, harmonic 0's zeroed as the reference does) from
+        seeds[b] unless given, then the generator."""
+        B, _, T = z.shape
+        L, H, dev = T * self.upp, self.n_harm, z.device
+        if B > 1:
+            # one generator pass per clip: the conv engine picks its tile width and split-K from the whole grid, so a
+            # batched launch may sum (and, without |max| cells, scale) in another order than the clip's own launch
+            # does -- per clip, decode_batch is bit-identical to B single-clip calls
+            if len(seeds) != B:
+                raise ValueError("decode_batch: one seed per clip")
+            sl = lambda t, b: None if t is None else t[b:b + 1]  # noqa: E731
+            return torch.cat([self._decode_vocoder(
+                z[b:b + 1], nsff0.reshape(B, T)[b:b + 1], gc, sl(sine_noise, b), (seeds[b],), sl(phase0, b),
+                None if adain_noise is None else [n[b:b + 1] for n in adain_noise]) for b in range(B)])
+        if (sine_noise is None or phase0 is None or (self.kind == "refinegan" and adain_noise is None)) \
+                and len(seeds) != B:
+            raise ValueError("decode_batch: one seed per clip")
+        if sine_noise is None:
+            sine_noise = torch.empty(B, L, H, device=dev)
+            for b in range(B):
+                ops.randn(sine_noise[b], seeds[b], ops.OFF_SINE)
+        else:
+            sine_noise = sine_noise.to(dev, torch.float32).reshape(B, L, H).contiguous()
+        if phase0 is None:
+            phase0 = torch.empty(B, H, device=dev)
+            for b in range(B):
+                ops.rand_uniform(phase0[b], seeds[b], ops.OFF_PHASE)
+        else:
+            phase0 = phase0.to(dev, torch.float32).reshape(B, H).clone()
+        phase0[:, 0].zero_()  # rand_ini[:, 0] = 0
+        f0 = nsff0.reshape(B, T).float().contiguous()
+        gdec = gc[4 * 6 * self.hidden:]
+        if self.kind == "mrf":
+            o = self.generator(z, f0, gdec, T, sine_noise, B, phase0=phase0)
+        else:
+            if adain_noise is not None:
+                shapes = self.adain_shapes(T)
+                if len(adain_noise) != len(shapes):
+                    raise ValueError(f"decode_batch: {len(shapes)} AdaIN draws expected, got {len(adain_noise)}")
+                adain_noise = [n.to(dev, torch.float32).reshape(B, C, Lk).contiguous()
+                               for n, (C, Lk) in zip(adain_noise, shapes)]
+            o = self.generator_refinegan(z, f0, gdec, T, sine_noise, phase0, B, adain_noise, tuple(seeds))
+        return o.view(B, L)
+
+    def decode_batch(self, z, nsff0, gc, sine_noise=None, seeds=(0,), phase0=None, adain_noise=None):
+        """The generator on z [B][inter][T] (synthesizers.py:461-465) -> o [B][T*upp]; clip b's draws from seeds[b].
+        Parity inputs (None: drawn on the device): sine_noise [B][L] ([B][L][H] for MRF-HiFi-GAN and RefineGAN, H = 9
+        and 1), phase0 [B][H] the source's torch.rand initial phases (MRF-HiFi-GAN, RefineGAN), adain_noise the list
+        of RefineGAN's AdaIN draws [B][C][L] in the reference's draw order."""
+        if self.kind != "nsf":
+            return self._decode_vocoder(z, nsff0, gc, sine_noise, seeds, phase0, adain_noise)
         B, _, T = z.shape
         L = T * self.upp
         if sine_noise is None:
@@ -363,22 +572,25 @@ class SynthesizerAMD:
                                              None if z_noise is None else z_noise.reshape(1, self.inter, T), (seed,))
         return z[0], z_p[0], stats[0], gc
 
-    def decode_cf(self, z, nsff0, gc, sine_noise=None, seed: int = 0):
-        """The NSF generator on z [inter][T] (synthesizers.py:461-465) -> o [T*upp]."""
+    def decode_cf(self, z, nsff0, gc, sine_noise=None, seed: int = 0, phase0=None, adain_noise=None):
+        """The generator on z [inter][T] (synthesizers.py:461-465) -> o [T*upp]."""
         T = z.shape[-1]
-        return self.decode_batch(z.reshape(1, self.inter, T), nsff0, gc, sine_noise, (seed,)).view(-1)
+        return self.decode_batch(z.reshape(1, self.inter, T), nsff0, gc, sine_noise, (seed,), phase0=phase0,
+                                 adain_noise=adain_noise).view(-1)
 
-    def infer_cf(self, phone_cf, pitch, nsff0, sid: int, z_noise=None, sine_noise=None, seed: int = 0):
+    def infer_cf(self, phone_cf, pitch, nsff0, sid: int, z_noise=None, sine_noise=None, seed: int = 0, phase0=None,
+                 adain_noise=None):
         """Channels-first core: phone [E][T], pitch int64 [T], nsff0 f32 [T] -> (o [T*upp], z, z_p, stats)."""
         z, z_p, stats, gc = self.prior_cf(phone_cf, pitch, sid, z_noise, seed)
-        return self.decode_cf(z, nsff0, gc, sine_noise, seed), z, z_p, stats
+        return self.decode_cf(z, nsff0, gc, sine_noise, seed, phase0, adain_noise), z, z_p, stats
 
     def infer(self, phone, phone_lengths, pitch=None, nsff0=None, sid=None, rate=None, z_noise=None,
-              sine_noise=None, seed: int = 0):
+              sine_noise=None, seed: int = 0, phase0=None, adain_noise=None):
         """Synthesizer.infer signature (synthesizers.py:446): phone [1, T, E] -> (o [1,1,L], x_mask, (z, z_p, m_p, logs_p)).
 
-        z_noise [1, inter, T] / sine_noise [1, T*upp, 1] inject the reference's randn_like draws
-        (parity mode); None draws them on the device (Philox, ``seed``)."""
+        z_noise [1, inter, T] / sine_noise [1, T*upp, 1] ([1, T*upp, 9] for MRF-HiFi-GAN) inject the reference's
+        randn_like draws (parity mode), phase0 [1, H] its torch.rand initial phases and adain_noise the list of
+        RefineGAN's AdaIN draws in draw order (decode_batch); None draws them on the device (Philox, ``seed``)."""
         if rate is not None:
             raise NotImplementedError("rate (partial inference) is not used by VC.pipeline")
         if pitch is None or nsff0 is None:
@@ -393,7 +605,7 @@ class SynthesizerAMD:
         ops.transpose(phone.contiguous().float(), phone_cf, 1, T, E)
         sid_i = int(sid.reshape(-1)[0]) if torch.is_tensor(sid) else int(sid)
         o, z, z_p, stats = self.infer_cf(phone_cf, pitch.reshape(T).to(torch.int64).contiguous(), nsff0, sid_i,
-                                         z_noise, sine_noise, seed)
+                                         z_noise, sine_noise, seed, phase0, adain_noise)
         m_p, logs_p = stats[: self.inter], stats[self.inter:]
         x_mask = torch.ones(1, 1, T, device=dev)
         return o.view(1, 1, -1), x_mask, (z.unsqueeze(0), z_p.unsqueeze(0), m_p.unsqueeze(0), logs_p.unsqueeze(0))

@@ -73,30 +73,19 @@ def _conv(g: _Gen, sd, name, co, ci, k, gain=1.0, bias=True):
         sd[name + ".bias"] = g.normal((co,), 0.02)
 
 
-def synth_state_dict(cfg: list, seed: int = 1234, emb_dim: int = 768) -> "OrderedDict[str, torch.Tensor]":
-    """fp32 state dict of ``Synthesizer`` minus ``enc_q`` (``synthesizers.py:396-426``)."""
-    (_, _, inter, hidden, filt, n_heads, n_layers, ksz, _, _, rks, rds, ur, uic, uks, spk, gin, sr) = cfg
-    g = _Gen(seed)
-    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
-    kc = hidden // n_heads
-    # TextEncoder (synthesizers.py:350-371)
-    sd["enc_p.emb_phone.weight"] = g.normal((hidden, emb_dim), 1.0 / math.sqrt(emb_dim))
-    sd["enc_p.emb_phone.bias"] = g.normal((hidden,), 0.02)
-    sd["enc_p.emb_pitch.weight"] = g.normal((256, hidden), 0.1)
-    for i in range(n_layers):
-        p = f"enc_p.encoder.attn_layers.{i}."
-        sd[p + "emb_rel_k"] = g.normal((1, 21, kc), kc ** -0.5)
-        sd[p + "emb_rel_v"] = g.normal((1, 21, kc), kc ** -0.5)
-        for n in ("q", "k", "v", "o"):
-            _conv(g, sd, p + f"conv_{n}", hidden, hidden, 1)
-        sd[f"enc_p.encoder.norm_layers_1.{i}.gamma"] = g.uniform((hidden,), 0.8, 1.2)
-        sd[f"enc_p.encoder.norm_layers_1.{i}.beta"] = g.normal((hidden,), 0.05)
-        _conv(g, sd, f"enc_p.encoder.ffn_layers.{i}.conv_1", filt, hidden, ksz)
-        _conv(g, sd, f"enc_p.encoder.ffn_layers.{i}.conv_2", hidden, filt, ksz)
-        sd[f"enc_p.encoder.norm_layers_2.{i}.gamma"] = g.uniform((hidden,), 0.8, 1.2)
-        sd[f"enc_p.encoder.norm_layers_2.{i}.beta"] = g.normal((hidden,), 0.05)
-    _conv(g, sd, "enc_p.proj", inter * 2, hidden, 1, gain=0.5)
-    # GeneratorNSF (synthesizers.py:114-161)
+MRF_NAMES = ("MRF-HiFi-GAN", "MRF HiFi-GAN")  # both spellings synthesizers.py:420 accepts
+VOCODERS = ("Default",) + MRF_NAMES + ("RefineGAN",)
+
+
+def _wn_conv(g: _Gen, sd, name, co, ci, k, std, bias=True):
+    """A weight-normed Conv1d in the reference's key order (bias, weight_g, weight_v)."""
+    if bias:
+        sd[name + ".bias"] = g.normal((co,), 0.02)
+    _wn(g, sd, name, (co, ci, k), std)
+
+
+def _dec_nsf(g: _Gen, sd, inter, rks, rds, ur, uic, uks, gin):
+    """GeneratorNSF (synthesizers.py:114-161)."""
     sd["dec.m_source.l_linear.weight"] = g.uniform((1, 1), 0.5, 1.5)
     sd["dec.m_source.l_linear.bias"] = g.normal((1,), 0.02)
     _conv(g, sd, "dec.conv_pre", uic, inter, 7)
@@ -121,6 +110,96 @@ def synth_state_dict(cfg: list, seed: int = 1234, emb_dim: int = 768) -> "Ordere
             j += 1
     sd["dec.conv_post.weight"] = g.normal((1, chans[-1], 7), 1.0 / math.sqrt(chans[-1] * 7))
     _conv(g, sd, "dec.cond", uic, gin, 1, gain=0.5)
+
+
+def _dec_mrf(g: _Gen, sd, inter, rks, rds, ur, uic, uks, gin):
+    """HiFiGANMRFGenerator (mrf_hifigan.py:96-120), harmonic_num = 8."""
+    sd["dec.m_source.l_linear.weight"] = g.uniform((1, 9), -1.5, 1.5)
+    sd["dec.m_source.l_linear.bias"] = g.normal((1,), 0.02)
+    _wn_conv(g, sd, "dec.conv_pre", uic, inter, 7, 1.0 / math.sqrt(inter * 7))
+    nup = len(ur)
+    chans = [uic // (2 ** (i + 1)) for i in range(nup)]
+    strides = [math.prod(ur[i + 1:]) if i + 1 < nup else 1 for i in range(nup)]
+    for i, (u, k) in enumerate(zip(ur, uks)):
+        cin = uic // (2 ** i)
+        sd[f"dec.upsamples.{i}.bias"] = g.normal((chans[i],), 0.02)
+        _wn(g, sd, f"dec.upsamples.{i}", (cin, chans[i], k), 1.0 / math.sqrt(cin * k / u))
+        s = strides[i]
+        kn = 1 if s == 1 else s * 2 - s % 2
+        _conv(g, sd, f"dec.noise_convs.{i}", chans[i], 1, kn, gain=0.5)
+    for i in range(nup):
+        c = chans[i]
+        for j, (k, ds) in enumerate(zip(rks, rds)):
+            for m in range(len(ds)):
+                for nm in ("conv1", "conv2"):
+                    _wn_conv(g, sd, f"dec.mrfs.{i}.{j}.layers.{m}.{nm}", c, c, k, 0.5 / math.sqrt(c * k))
+    _wn_conv(g, sd, "dec.conv_post", 1, chans[-1], 7, 1.0 / math.sqrt(chans[-1] * 7))
+    _conv(g, sd, "dec.cond", uic, gin, 1, gain=0.5)
+
+
+def _dec_refinegan(g: _Gen, sd, inter, ur, gin):
+    """RefineGANGenerator (refinegan.py:109-144): 512 initial channels whatever the config says; the config's
+    upsample kernel sizes and resblock lists are not read."""
+    ch = 512
+    sd["dec.m_source.merge.0.weight"] = g.uniform((1, 1), 0.8, 1.6)
+    _wn_conv(g, sd, "dec.pre_conv", ch // 2, 1, 7, 2.0 / math.sqrt(7))
+    nup = len(ur)
+    strides = [math.prod(ur[i + 1:]) if i + 1 < nup else 1 for i in range(nup)]
+    for i in range(nup):
+        s = strides[i]
+        kn = 1 if s == 1 else s * 2 - s % 2
+        _wn_conv(g, sd, f"dec.downsample_blocks.{i}", ch // 2 ** (i + 2), 1, kn, 1.0 / math.sqrt(kn))
+    _wn_conv(g, sd, "dec.mel_conv", ch // 2, inter, 7, 1.0 / math.sqrt(inter * 7))
+    _conv(g, sd, "dec.cond", ch // 2, gin, 1, gain=0.5)
+    c = ch
+    for i in range(nup):
+        new = c // 2
+        p = f"dec.upsample_conv_blocks.{i}."
+        _conv(g, sd, p + "input_conv", new, c + c // 4, 7)
+        for j, k in enumerate((3, 7, 11)):
+            # AdaIN weights differ per channel (and per layer): a kernel indexing them wrongly shows
+            sd[p + f"blocks.{j}.0.weight"] = g.uniform((new,), 0.05, 0.4)
+            for m in range(3):
+                for nm in ("convs1", "convs2"):
+                    _wn_conv(g, sd, p + f"blocks.{j}.1.{nm}.{m}", new, new, k, 0.5 / math.sqrt(new * k))
+            sd[p + f"blocks.{j}.2.weight"] = g.uniform((new,), 0.05, 0.4)
+        c = new
+    _wn_conv(g, sd, "dec.conv_post", 1, c, 7, 1.0 / math.sqrt(c * 7), bias=False)
+
+
+def synth_state_dict(cfg: list, seed: int = 1234, emb_dim: int = 768,
+                     vocoder: str = "Default") -> "OrderedDict[str, torch.Tensor]":
+    """fp32 state dict of ``Synthesizer`` minus ``enc_q`` (``synthesizers.py:396-426``); ``vocoder`` picks the
+    decoder's layout as synthesizers.py:418-421 does ("Default" draws exactly what it always drew)."""
+    (_, _, inter, hidden, filt, n_heads, n_layers, ksz, _, _, rks, rds, ur, uic, uks, spk, gin, sr) = cfg
+    if vocoder not in VOCODERS:
+        raise ValueError(f"vocoder must be one of {VOCODERS}, got {vocoder!r}")
+    g = _Gen(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    kc = hidden // n_heads
+    # TextEncoder (synthesizers.py:350-371)
+    sd["enc_p.emb_phone.weight"] = g.normal((hidden, emb_dim), 1.0 / math.sqrt(emb_dim))
+    sd["enc_p.emb_phone.bias"] = g.normal((hidden,), 0.02)
+    sd["enc_p.emb_pitch.weight"] = g.normal((256, hidden), 0.1)
+    for i in range(n_layers):
+        p = f"enc_p.encoder.attn_layers.{i}."
+        sd[p + "emb_rel_k"] = g.normal((1, 21, kc), kc ** -0.5)
+        sd[p + "emb_rel_v"] = g.normal((1, 21, kc), kc ** -0.5)
+        for n in ("q", "k", "v", "o"):
+            _conv(g, sd, p + f"conv_{n}", hidden, hidden, 1)
+        sd[f"enc_p.encoder.norm_layers_1.{i}.gamma"] = g.uniform((hidden,), 0.8, 1.2)
+        sd[f"enc_p.encoder.norm_layers_1.{i}.beta"] = g.normal((hidden,), 0.05)
+        _conv(g, sd, f"enc_p.encoder.ffn_layers.{i}.conv_1", filt, hidden, ksz)
+        _conv(g, sd, f"enc_p.encoder.ffn_layers.{i}.conv_2", hidden, filt, ksz)
+        sd[f"enc_p.encoder.norm_layers_2.{i}.gamma"] = g.uniform((hidden,), 0.8, 1.2)
+        sd[f"enc_p.encoder.norm_layers_2.{i}.beta"] = g.normal((hidden,), 0.05)
+    _conv(g, sd, "enc_p.proj", inter * 2, hidden, 1, gain=0.5)
+    if vocoder in MRF_NAMES:
+        _dec_mrf(g, sd, inter, rks, rds, ur, uic, uks, gin)
+    elif vocoder == "RefineGAN":
+        _dec_refinegan(g, sd, inter, ur, gin)
+    else:
+        _dec_nsf(g, sd, inter, rks, rds, ur, uic, uks, gin)
     # ResidualCouplingBlock (residuals.py:71-140) + WaveNet (modules.py:9-59)
     half = inter // 2
     for f in range(4):
@@ -139,10 +218,10 @@ def synth_state_dict(cfg: list, seed: int = 1234, emb_dim: int = 768) -> "Ordere
     return sd
 
 
-def make_synth_ckpt(sr: int = 48000, version: str = "v2", seed: int = 1234) -> dict:
+def make_synth_ckpt(sr: int = 48000, version: str = "v2", seed: int = 1234, vocoder: str = "Default") -> dict:
     """A voice-model checkpoint dict in the ``train.py:729-742`` layout (fp16 weights)."""
     cfg = synth_config(sr, version)
-    sd = synth_state_dict(cfg, seed, emb_dim=768 if version == "v2" else 256)
+    sd = synth_state_dict(cfg, seed, emb_dim=768 if version == "v2" else 256, vocoder=vocoder)
     opt = OrderedDict(weight=OrderedDict((k, v.half()) for k, v in sd.items()))
     opt["config"] = cfg
     opt["epoch"] = "1epoch"
@@ -151,7 +230,7 @@ def make_synth_ckpt(sr: int = 48000, version: str = "v2", seed: int = 1234) -> d
     opt["f0"] = 1
     opt["version"] = version
     opt["model_name"] = f"synthetic_{sr // 1000}k_{version}_s{seed}"
-    opt["vocoder"] = "Default"
+    opt["vocoder"] = vocoder
     return opt
 
 

@@ -130,6 +130,9 @@ typedef struct rvc_conv1d_args {
 int64_t rvc_conv1d_workspace_bytes(const rvc_conv1d_args* a);
 /* Which engine a call would run on: 0 = f32 MFMA, 1 = split-bf16 (x6); -1 on bad args. */
 int rvc_conv1d_engine(const rvc_conv1d_args* a);
+/* The output tile a call's blocks would compute: (rows << 16) | columns, e.g. 128 x 256 = 0x800100; -1 on bad args.
+ * The choice depends on the shape, the pass set and the device's CU count (how the tile grid fills its rounds). */
+int rvc_conv1d_tile(const rvc_conv1d_args* a);
 int rvc_conv1d(const rvc_conv1d_args* a, void* ws, int64_t ws_bytes, rvc_stream_t stream);
 /* Profiling hook (this host thread): while set to a hipEvent_t, each rvc_conv1d call records it on its stream
  * right after the conv kernel, before any split-K reduce, so that a caller's events can bracket the conv

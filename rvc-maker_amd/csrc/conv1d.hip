@@ -115,25 +115,55 @@ __device__ __forceinline__ void apply_act(floatx4 (&acc)[FM][FN], float slope, f
 // l&15, rows (l>>4)*4 + r of each fragment).  Split-K partial tiles go to the workspace (summed in split
 // order by conv_splitk_reduce); otherwise bias, 2nd bias, activation, scale, residual, accumulate and the
 // (strided / polyphase / masked) store are fused here.
+// The split-K part: a block's raw partial tile into its slab of the workspace.
 template <int FM, int FN, int WM, int WN>
+__device__ __forceinline__ void conv_store_partial(const ConvParams& p, floatx4 (&acc)[FM][FN], int lane, int wm, int wn,
+                                                   int split, int phase, int b, int g, int Cog, int m0g, int64_t n0) {
+    const int ln = lane & 15;
+    const int lr = (lane >> 4) * 4;
+    float* wsb = p.ws + (((int64_t)split * p.B * p.nphase + (int64_t)b * p.nphase + phase) * p.Co) * p.ncols;
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int mg = m0g + wm * 16 * FM + i * 16 + lr + r;
+            const int64_t m = (int64_t)g * Cog + mg;
+#pragma unroll
+            for (int j = 0; j < FN; ++j) {
+                const int64_t n = n0 + wn * 16 * FN + j * 16 + ln;
+                if (mg < Cog && n < p.ncols) wsb[m * p.ncols + n] = acc[i][j][r];
+            }
+        }
+}
+
+// The x6 engine's epilogue constants (round 8): a [3][BM] float table in the block's LDS, filled once per block by the
+// compute waves before the chunk-0 barrier -- row r of the tile: [0] the split-fp16 reciprocal weight scale (1 otherwise),
+// [1] bias, [2] bias2.  A null bias is stored as +0.f and a null bias2 as -0.f, so that "bs = bias; bs += bias2" gives
+// the bits of the guarded form in every case (x + -0.f == x for every x; both null: +0.f, as before).  The epilogues
+// read it with ds_read: before, each row fragment pass waited a global round trip per row for bias[row] / bias2[row]
+// (8 serial vmcnt(0) round trips per pass on the 128 x 256 tile, each also behind the previous pass's 64 stores).
+// TB = false (the f32 MFMA engine): the constants from global memory, as before.
+template <bool TB, int BM>
+__device__ __forceinline__ float epi_bias(const ConvParams& p, const float* tb, int rl, int mrow) {
+    float bs = 0.f;
+    if constexpr (TB) {
+        bs = tb[BM + rl];
+        bs += tb[2 * BM + rl];
+    } else {
+        if (p.bias) bs = p.bias[mrow];
+        if (p.bias2) bs += p.bias2[mrow];
+    }
+    return bs;
+}
+
+template <int FM, int FN, int WM, int WN, bool TB = false>
 __device__ __forceinline__ void conv_epilogue(const ConvParams& p, floatx4 (&acc)[FM][FN], int lane, int wm, int wn,
-                                              int split, int phase, int b, int g, int Cog, int m0g, int64_t n0) {
+                                              int split, int phase, int b, int g, int Cog, int m0g, int64_t n0,
+                                              const float* tb = nullptr) {
     const int ln = lane & 15;
     const int lr = (lane >> 4) * 4;
     if (p.ksplit > 1) {
-        float* wsb = p.ws + (((int64_t)split * p.B * p.nphase + (int64_t)b * p.nphase + phase) * p.Co) * p.ncols;
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int mg = m0g + wm * 16 * FM + i * 16 + lr + r;
-                const int64_t m = (int64_t)g * Cog + mg;
-#pragma unroll
-                for (int j = 0; j < FN; ++j) {
-                    const int64_t n = n0 + wn * 16 * FN + j * 16 + ln;
-                    if (mg < Cog && n < p.ncols) wsb[m * p.ncols + n] = acc[i][j][r];
-                }
-            }
+        conv_store_partial<FM, FN, WM, WN>(p, acc, lane, wm, wn, split, phase, b, g, Cog, m0g, n0);
         return;
     }
     // Epilogue one row fragment (16 channels x BN/WN columns) at a time, in passes so that hipcc
@@ -158,9 +188,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, floatx4 (&acc
             const int mg = m0g + wm * 16 * FM + i * 16 + lr + r;
             mok[r] = mg < Cog;
             mrow[r] = g * Cog + (mg < Cog ? mg : 0);
-            float bs = 0.f;
-            if (p.bias) bs = p.bias[mrow[r]];
-            if (p.bias2) bs += p.bias2[mrow[r]];
+            const float bs = epi_bias<TB, 16 * FM * WM>(p, tb, wm * 16 * FM + i * 16 + lr + r, mrow[r]);
 #pragma unroll
             for (int j = 0; j < FN; ++j) av[0][j][r] += bs;
         }
@@ -209,7 +237,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, floatx4 (&acc
 // the same order per element as conv_epilogue, so the same bits.
 template <int FM, int FN, int WM, int WN>
 __device__ __forceinline__ void conv_epilogue_swz(const ConvParams& p, floatx4 (&acc)[FM][FN], int lane, int wm, int wn,
-                                                  int phase, int b, int g, int Cog, int m0g, int64_t n0) {
+                                                  int phase, int b, int g, int Cog, int m0g, int64_t n0,
+                                                  const float* tb) {
     static_assert(FN % 2 == 0, "column fragments in pairs");
     constexpr int NP = FN / 2;
     const int h = lane >> 5, lc = lane & 31;
@@ -240,9 +269,7 @@ __device__ __forceinline__ void conv_epilogue_swz(const ConvParams& p, floatx4 (
             const int mg = m0g + wm * 16 * FM + i * 16 + 8 * h + k;
             mok[k] = mg < Cog;
             mrow[k] = g * Cog + (mg < Cog ? mg : 0);
-            float bs = 0.f;
-            if (p.bias) bs = p.bias[mrow[k]];
-            if (p.bias2) bs += p.bias2[mrow[k]];
+            const float bs = epi_bias<true, 16 * FM * WM>(p, tb, wm * 16 * FM + i * 16 + 8 * h + k, mrow[k]);
 #pragma unroll
             for (int jp = 0; jp < NP; ++jp) av[0][2 * jp + (k >> 2)][k & 3] += bs;
         }
@@ -282,6 +309,189 @@ __device__ __forceinline__ void conv_epilogue_swz(const ConvParams& p, floatx4 (
                 }
             }
     }
+    if (p.amax_out) amax_publish(p.amax_out + (int64_t)b * RVC_AMAX_SHARDS, amx);
+}
+
+// The in-register epilogue of the 256-wide x6 tile (round 8), in either register layout (SWZ: conv_epilogue_swz's
+// 128-byte rows, else conv_epilogue's), with the addresses as ONE scalar row base per row plus ONE 32-bit per-lane byte
+// offset per column group (global_load / global_store with an SGPR base): the forms above keep a 64-bit address per
+// element -- 32 per class of loads and per pass -- and with the tile's 64 accumulators that spilled 47 VGPRs, all in
+// the epilogue, the second pass's accumulators among them (reloaded one by one behind vmcnt(0), in order behind the
+// first pass's 64 stores).  wm is wave-uniform (the kernel takes the wave index through readfirstlane), so a row
+// fragment's 16 rows are valid or not for the whole wave: fragments past Co are skipped and no address needs a per-lane
+// row clamp (plan() gives the 256-wide tile only to Co % 16 == 0, and to rows < 2^26 elements: 32-bit byte offsets).
+// PART: the split-K block's raw partial tile into its slab of the workspace (conv_store_partial's stores) in the same
+// form.  (Issuing the residual AND the accumulate loads of a pass before the first add put the accumulators into
+// scratch inside the chunk loop: not kept.)  The same operations in the same order per element as conv_epilogue, so
+// the same bits.
+template <int FM, int FN, int WM, int WN, bool SWZ, bool PART = false>
+__device__ __forceinline__ void conv_epilogue_rows(const ConvParams& p, floatx4 (&acc)[FM][FN], int lane, int wm, int wn,
+                                                   int split, int phase, int b, int g, int Cog, int m0g, int64_t n0,
+                                                   const float* tb, float* scr) {
+    static_assert(!(SWZ && PART), "split-K partial tiles keep the accumulator layout");
+    static_assert(FN % 2 == 0, "column fragments in pairs");
+    constexpr int BM = 16 * FM * WM;
+    constexpr int NV = SWZ ? FN / 2 : FN;  // column groups per lane
+    constexpr int NR = SWZ ? 8 : 4;        // rows per lane and fragment
+    constexpr int CW = SWZ ? 32 : 16;      // lanes along a row
+// element (row kr, column group jv) of row fragment i: the register it lives in (after the swaps when SWZ)
+#define X6_EL(kr, jv) acc[i][SWZ ? 2 * (jv) + ((kr) >> 2) : (jv)][SWZ ? ((kr) & 3) : (kr)]
+    const int lrow = SWZ ? (lane >> 5) * 8 : (lane >> 4) * 4;
+    const int lcol = lane & (CW - 1);
+    const int Lo = PART ? (int)p.ncols : (int)p.Lout;  // the destination's row length
+    const int64_t c0 = n0 + wn * 16 * FN + lcol;
+    auto col_pos = [&](int jv) __attribute__((always_inline)) {
+        const int64_t n = c0 + jv * CW;
+        if constexpr (PART) return n < p.ncols ? (int)n : -1;
+        else return out_pos(p, n, phase);
+    };
+    uint32_t voff[NV];  // byte offset of (the lane's first row, its column jv) from the fragment's first row
+    unsigned okm = 0;   // columns that are stored
+#pragma unroll
+    for (int jv = 0; jv < NV; ++jv) {
+        const int t = col_pos(jv);
+        okm |= (unsigned)(t >= 0) << jv;
+        voff[jv] = (uint32_t)(lrow * Lo + (t >= 0 ? t : 0)) * 4u;
+    }
+    // PART: the block's slab of the split-K workspace, raw sums (conv_store_partial's stores)
+    float* yb = PART ? p.ws + (((int64_t)split * p.B * p.nphase + (int64_t)b * p.nphase + phase) * p.Co) * p.ncols
+                     : p.y + b * p.y_bstride;
+    const float* rb2 = !PART && p.res ? p.res + b * p.res_bstride : nullptr;
+    const bool accum = !PART && p.accumulate;
+    const bool allok = __builtin_amdgcn_ballot_w64(okm != (1u << NV) - 1u) == 0;  // wave-uniform
+    const size_t rowb = (size_t)Lo * 4;
+    float amx = 0.f;
+    // The passes once per case of (all columns stored, residual, accumulate) for the full tiles, as straight-line code:
+    // with these as run-time branches inside the passes hipcc's wait bookkeeping merged the paths at every join and
+    // put a vmcnt(0) -- a wait for the first pass's 32 stores -- in front of the second pass.  SPEC < 0: the run-time
+    // form (a row's last column tile).
+    auto run = [&](auto spec_c) __attribute__((always_inline)) {
+        constexpr int SPEC = decltype(spec_c)::value;
+        const bool all = SPEC < 0 ? allok : true;
+        const bool has_res = SPEC < 0 ? rb2 != nullptr : (SPEC & 1) != 0;
+        const bool has_acc = SPEC < 0 ? accum : (SPEC & 2) != 0;
+#pragma unroll
+        for (int i = 0; i < FM; ++i) {
+            const int srow = m0g + wm * 16 * FM + i * 16;  // wave-uniform
+            if (srow >= Cog) continue;  // (whole fragments: plan() gives this tile only to Co % 16 == 0)
+            if constexpr (SWZ) {
+#pragma unroll
+                for (int jp = 0; jp < FN / 2; ++jp)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[i][2 * jp][r]),
+                                                                         __float_as_uint(acc[i][2 * jp + 1][r]), false, false);
+                        acc[i][2 * jp][r] = __uint_as_float(sw[0]);
+                        acc[i][2 * jp + 1][r] = __uint_as_float(sw[1]);
+                    }
+            }
+            if constexpr (!PART) {
+                floatx4 (&av)[1][FN] = *reinterpret_cast<floatx4 (*)[1][FN]>(&acc[i][0]);
+#pragma unroll
+                for (int kr = 0; kr < NR; ++kr) {
+                    const float bs = epi_bias<true, BM>(p, tb, wm * 16 * FM + i * 16 + lrow + kr, 0);
+#pragma unroll
+                    for (int jv = 0; jv < NV; ++jv) X6_EL(kr, jv) += bs;
+                }
+                // The transcendental activations one value at a time in a rolled loop, through the wave's own 4 KB of the
+                // block's LDS (scr: the X buffers are dead after the last chunk's barrier; lane-private slots, so no barrier):
+                // unrolled over a row fragment beside the tile's 64 accumulators their expansions spilled 16 and more VGPRs,
+                // and the allocator then kept four of the second pass's accumulators in scratch on every path.  Same
+                // function of the same value, so the same bits.
+                const int oa = p.out_act;
+                if (oa == RVC_ACT_TANH || oa == RVC_ACT_GELU || oa == RVC_ACT_SIGMOID || oa == RVC_ACT_LOGCLAMP) {
+#pragma unroll
+                    for (int q0 = 0; q0 < FN; q0 += 4) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) scr[(q * 4 + r) * 64 + lane] = av[0][q0 + q][r];
+#pragma unroll 1
+                        for (int e = 0; e < 16; ++e) {
+                            const float v = scr[e * 64 + lane];
+                            scr[e * 64 + lane] = act_apply(v, oa, p.out_slope) * p.out_scale;
+                        }
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) av[0][q0 + q][r] = scr[(q * 4 + r) * 64 + lane];
+                    }
+                } else if (oa == RVC_ACT_LRELU) {
+                    apply_act<RVC_ACT_LRELU, 1, FN>(av, p.out_slope, p.out_scale);
+                } else if (oa == RVC_ACT_RELU) {
+                    apply_act<RVC_ACT_RELU, 1, FN>(av, p.out_slope, p.out_scale);
+                } else {
+                    apply_act<RVC_ACT_NONE, 1, FN>(av, p.out_slope, p.out_scale);
+                }
+            }
+            const int64_t ro = (int64_t)(g * Cog + srow) * Lo;  // wave-uniform: the fragment's first row
+            char* ybase = reinterpret_cast<char*>(yb + ro);
+            if (has_res) {
+                const char* rbase = reinterpret_cast<const char*>(rb2 + ro);
+                float rv[NR][NV];
+#pragma unroll
+                for (int kr = 0; kr < NR; ++kr)
+#pragma unroll
+                    for (int jv = 0; jv < NV; ++jv) rv[kr][jv] = *reinterpret_cast<const float*>(rbase + kr * rowb + voff[jv]);
+#pragma unroll
+                for (int kr = 0; kr < NR; ++kr)
+#pragma unroll
+                    for (int jv = 0; jv < NV; ++jv) X6_EL(kr, jv) += rv[kr][jv];
+            }
+            if (has_acc) {
+                float yv[NR][NV];
+#pragma unroll
+                for (int kr = 0; kr < NR; ++kr)
+#pragma unroll
+                    for (int jv = 0; jv < NV; ++jv) yv[kr][jv] = *reinterpret_cast<const float*>(ybase + kr * rowb + voff[jv]);
+#pragma unroll
+                for (int kr = 0; kr < NR; ++kr)
+#pragma unroll
+                    for (int jv = 0; jv < NV; ++jv) X6_EL(kr, jv) += yv[kr][jv];
+            }
+            if (all) {  // every column of the wave's tile is stored (all but a row's last tile): straight-line stores
+#pragma unroll
+                for (int kr = 0; kr < NR; ++kr)
+#pragma unroll
+                    for (int jv = 0; jv < NV; ++jv) {
+                        const float v = X6_EL(kr, jv);
+                        *reinterpret_cast<float*>(ybase + kr * rowb + voff[jv]) = v;
+                        amx = fmaxf(amx, fabsf(v));
+                    }
+            } else {
+#pragma unroll
+                for (int kr = 0; kr < NR; ++kr)
+#pragma unroll
+                    for (int jv = 0; jv < NV; ++jv) {
+                        const float v = X6_EL(kr, jv);
+                        if ((okm >> jv) & 1u) {
+                            *reinterpret_cast<float*>(ybase + kr * rowb + voff[jv]) = v;
+                            amx = fmaxf(amx, fabsf(v));
+                        }
+                    }
+            }
+        }
+    };
+    if (!allok) run(std::integral_constant<int, -1>{});
+    else if (rb2 && accum) run(std::integral_constant<int, 3>{});
+    else if (rb2) run(std::integral_constant<int, 1>{});
+    else if (accum) run(std::integral_constant<int, 2>{});
+    else run(std::integral_constant<int, 0>{});
+    if constexpr (PART) return;
+    if (p.wrap) {  // the border cells of a 2-D image are stored as 0: a pass of its own, off the 1-D path
+#pragma unroll 1
+        for (int i = 0; i < FM; ++i) {
+            const int srow = m0g + wm * 16 * FM + i * 16;
+            if (srow >= Cog) continue;
+#pragma unroll 1
+            for (int jv = 0; jv < NV; ++jv) {
+                const int t = col_pos(jv);
+                if (t > -2) continue;
+                for (int kr = 0; kr < NR; ++kr) yb[(int64_t)(g * Cog + srow + lrow + kr) * Lo + (-t - 2)] = 0.f;
+            }
+        }
+    }
+#undef X6_EL
     if (p.amax_out) amax_publish(p.amax_out + (int64_t)b * RVC_AMAX_SHARDS, amx);
 }
 
@@ -499,6 +709,8 @@ constexpr bool kAblations = RVC_CONV_ABLATIONS != 0;
 #endif
 #ifndef X6_NOBAR
 #define X6_NOBAR 0  // profiling ablation only: no per-chunk barrier (races, wrong results)
+// (the 256-wide tile's epilogue also counts on that barrier: after the last chunk's barrier the X buffers are dead, and
+// conv_epilogue_rows runs its rolled activations through them -- another reason this switch gives wrong results)
 #endif
 #if X6_NOBAR && !RVC_CONV_ABLATIONS
 #error "X6_NOBAR races (wrong results): only in a -DRVC_CONV_ABLATIONS=1 profiling build"
@@ -662,8 +874,10 @@ __global__ __launch_bounds__(64 * (WM * WN + 4), (x6_min_blocks<FM, FN, WM * WN,
     constexpr int NPL = NP == 6 ? 3 : (NP == 3 ? 2 : 1);
     constexpr int BM = 16 * FM * WM;
     constexpr int BN = 16 * FN * WN;
-    extern __shared__ uint4 xs[];  // [2 buffers][span][NPL planes][4 x 16 B]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    extern __shared__ uint4 xs[];  // [2 buffers][span][NPL planes][4 x 16 B], the tile |max|, the epilogue constants
+    const int tid = threadIdx.x, lane = tid & 63;
+    // the wave index as a scalar: wm, wn and every row / column base derived from them stay out of the VGPRs
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // XCD-aware tile order (cdna_hip_programming.md T1, the bijective form): blocks are dealt round-robin over
     // the 8 XCDs, so block b serves tile t(b), which gives each XCD a contiguous run of the row-major tile
     // order -- whole rows of column tiles, which read the same weight fragments, share that XCD's L2 instead
@@ -699,6 +913,7 @@ __global__ __launch_bounds__(64 * (WM * WN + 4), (x6_min_blocks<FM, FN, WM * WN,
     const int nck = ch_end - ch_beg;
     const int bufsz = NPL * span * 4;  // uint4 per buffer
     float* tmax = reinterpret_cast<float*>(xs + 2 * bufsz);  // F16: the 4 loader waves' tile |max|
+    float* etab = tmax + 4;                                  // [3][BM] epilogue constants (epi_bias)
     // Blocks co-resident on one XCD (ids = x mod 8) walk the k-steps from different starting
     // (chunk, tap): in lockstep they would all read the same few weight lines, i.e. the same L2 channels.
     const int rseed = p.rot ? (bx >> 3) : 0;
@@ -993,6 +1208,20 @@ __global__ __launch_bounds__(64 * (WM * WN + 4), (x6_min_blocks<FM, FN, WM * WN,
     const int s_beg = ch_beg * K, s_end = ch_end * K;
     const uint4* wxp = p.wx + (int64_t)phase * K * nch * nmf * 3 * 64;
     const int mf0 = m0g / 16 + wm * FM;
+    // the epilogue constants of the block's BM rows (epi_bias), one row per thread: the loads go first, ahead of the
+    // weight ring's, from unconditional addresses (a null bias reads the weight image and is replaced by its zero), and
+    // the values go into LDS just before the chunk-0 barrier -- no wait of their own beyond the ring's first
+    const float* rscale = reinterpret_cast<const float*>(p.wx + (int64_t)p.nphase * K * nch * nmf * 3 * 64);
+    float et_rs = 1.f, et_b1 = 0.f, et_b2 = -0.f;
+    if (tid < BM) {
+        const int mg = m0g + tid;
+        const int mr = grp * Cog + (mg < Cog ? mg : 0);
+        const float* wz = reinterpret_cast<const float*>(p.wx);
+        if constexpr (F16) et_rs = rscale[mg];
+        const float v1 = *(p.bias ? p.bias + mr : wz), v2 = *(p.bias2 ? p.bias2 + mr : wz);
+        et_b1 = p.bias ? v1 : 0.f;
+        et_b2 = p.bias2 ? v2 : -0.f;
+    }
     // weight fragments of logical k-step (chunk index i, tap index tl) -- chunk-major from s_beg
     auto aload = [&](int i, int tl, uint4 (&a)[NPL][FM]) __attribute__((always_inline)) {
         // wave-uniform fragment base (scalar registers) + one per-lane offset: saddr loads, no
@@ -1097,7 +1326,12 @@ __global__ __launch_bounds__(64 * (WM * WN + 4), (x6_min_blocks<FM, FN, WM * WN,
         }
         if (wave == 0) X6_STAMP(4, X6_NOW());
     }
-    __syncthreads();  // chunk 0 staged
+    if (tid < BM) {
+        etab[tid] = et_rs;
+        etab[BM + tid] = et_b1;
+        etab[2 * BM + tid] = et_b2;
+    }
+    __syncthreads();  // chunk 0 staged, the epilogue constants in LDS
     if constexpr (F16) {
         if (LF || p.amax_in) tile_rs = ldexpf(1.f, -f16_exp(fmaxf(fmaxf(tmax[0], tmax[1]), fmaxf(tmax[2], tmax[3]))));
     }
@@ -1136,12 +1370,11 @@ __global__ __launch_bounds__(64 * (WM * WN + 4), (x6_min_blocks<FM, FN, WM * WN,
     if constexpr (F16) {
         // undo both scales: row m's reciprocal weight scale (stored after the image) x the tile's (exact:
         // powers of 2), before split-K partials or the epilogue see the sums
-        const float* rs = reinterpret_cast<const float*>(p.wx + (int64_t)p.nphase * K * nch * nmf * 3 * 64);
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float f = rs[m0g + wm * 16 * FM + i * 16 + lg * 4 + r] * tile_rs;
+                const float f = etab[wm * 16 * FM + i * 16 + lg * 4 + r] * tile_rs;
 #pragma unroll
                 for (int j = 0; j < FN; ++j) acc[i][j][r] *= f;
             }
@@ -1159,10 +1392,7 @@ __global__ __launch_bounds__(64 * (WM * WN + 4), (x6_min_blocks<FM, FN, WM * WN,
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int mg = m0g + wm * 16 * FM + i * 16 + lg * 4 + r;
-                    const int mr = mg < Cog ? mg : 0;
-                    float bs = 0.f;
-                    if (p.bias) bs = p.bias[mr];
-                    if (p.bias2) bs += p.bias2[mr];
+                    const float bs = epi_bias<true, BM>(p, etab, wm * 16 * FM + i * 16 + lg * 4 + r, 0);
 #pragma unroll
                     for (int j = 0; j < FN; ++j) av[0][j][r] += bs;
                 }
@@ -1200,10 +1430,23 @@ __global__ __launch_bounds__(64 * (WM * WN + 4), (x6_min_blocks<FM, FN, WM * WN,
             __syncthreads();
             x6_tile_epilogue<BM / 2, BN, 64 * (NCW + 4)>(p, ot, tid, split, b, m0g + BM / 2, n0);
         }
+    } else if constexpr (FN == 8) {  // the 256-wide tile: the row-base forms (no per-element addresses, nothing spilled)
+        // the wave's 4 KB of the dead X buffers (>= 32 KB on this tile: span >= 256), for the rolled activations
+        // Dead because the loaders' last stores (guarded by i + 1 < nck) precede the last chunk's barrier, which X6_NOBAR
+        // removes: that ablation build races here too.
+        static_assert(NCW * 16 * 64 * 4 <= 2 * 256 * 64, "the rolled activations need 4 KB per compute wave of the X "
+                                                         "buffers' smallest size (2 buffers x 1 plane x span 256 x 64 B)");
+        static_assert(!X6_NOBAR || RVC_CONV_ABLATIONS, "the X buffers are reused after the last chunk's barrier");
+        float* scr = reinterpret_cast<float*>(xs) + wave * (16 * 64);
+        if (p.ksplit > 1)
+            conv_epilogue_rows<FM, FN, WM, WN, false, true>(p, acc, lane, wm, wn, split, ophase, b, grp, Cog, m0g, n0, etab, scr);
+        else if (p.swz)
+            conv_epilogue_rows<FM, FN, WM, WN, true>(p, acc, lane, wm, wn, 0, ophase, b, grp, Cog, m0g, n0, etab, scr);
+        else conv_epilogue_rows<FM, FN, WM, WN, false>(p, acc, lane, wm, wn, 0, ophase, b, grp, Cog, m0g, n0, etab, scr);
     } else if (p.swz && p.ksplit == 1) {
-        conv_epilogue_swz<FM, FN, WM, WN>(p, acc, lane, wm, wn, ophase, b, grp, Cog, m0g, n0);
+        conv_epilogue_swz<FM, FN, WM, WN>(p, acc, lane, wm, wn, ophase, b, grp, Cog, m0g, n0, etab);
     } else {
-        conv_epilogue<FM, FN, WM, WN>(p, acc, lane, wm, wn, split, ophase, b, grp, Cog, m0g, n0);
+        conv_epilogue<FM, FN, WM, WN, true>(p, acc, lane, wm, wn, split, ophase, b, grp, Cog, m0g, n0, etab);
     }
 #if RVC_CONV_STAMPS
     if (wave == 0) {
@@ -1591,7 +1834,17 @@ int plan(const rvc_conv1d_args* a, ConvParams& p, Cfg& cfg, dim3& grid, size_t& 
         const int64_t rows128 = (Cog + 127) / 128, nb = a->B * a->nphase;
         const bool fills256 = round_eff(rows128 * ((ncols + 255) / 256) * nb) >=
                               round_eff(rows128 * ((ncols + 127) / 128) * nb) - 0.05;
+        // (Co % 16 == 0 and rows < 2^26: the 256-wide tile's epilogue works on whole 16-row fragments and takes 32-bit byte
+        // offsets within 13 rows, conv_epilogue_rows; anything else runs 128 wide, the same sums.  The trade-off, reasoned
+        // and not measured: such a shape gives up what the wide tile gained over the narrow one above (7-12 % of the
+        // conv's time at C = 128 / 256) and is no slower than on the 128-wide tile, which it ran on before the wide one
+        // existed.  No model this library loads has one: the generators', encoders' and RMVPE's convs with more than 64 output
+        // channels per group have a multiple of 64 of them (but RMVPE's 512 -> 360 salience linear, one K = 1 launch of a
+        // few dozen tiles per clip on its f32 path), and a row holds at most 2^24 inputs (x6_eligible).  The
+        // alternative, a per-element path for a fragment that straddles Co, put the accumulators of EVERY wide instance
+        // into memory (272 B per lane), the hot ones included.)
         if (Cog > 64 && w8 && bn256 && a->stride == 1 && 255 + max_tap_off(a) + 1 <= 64 * X6_NI_MAX - 2 &&
+            Cog % 16 == 0 && a->Lout < (1ll << 26) && ncols < (1ll << 26) &&
             (bn256 == 2 || np == RVC_ARITH_F16X3) && (fills256 || bn256 == 3))
             cfg = {2, 8, 4, 2, true};
         else if (Cog > 64 && w8) cfg = {2, 4, 4, 2, true};  // 128 x 128 on 8 compute waves
@@ -1640,6 +1893,7 @@ int plan(const rvc_conv1d_args* a, ConvParams& p, Cfg& cfg, dim3& grid, size_t& 
                            BN <= 128;
         p.tile_epi = !(tepi && plain && a->groups == 1) ? 0
                      : tile_bytes <= lds ? 1 : (cfg.WM % 2 == 0 && tile_bytes / 2 <= lds) ? 2 : 0;
+        lds += (size_t)3 * BM * 4;  // the epilogue constants (epi_bias), behind the X buffers and the tile epilogue's tile
         grid = dim3(cdiv(ncols, BN), (unsigned)p.mtiles_per_group, (unsigned)(a->B * p.nphase * p.ksplit));
         RVC_CHECK_ARG(grid.y < 65536 && grid.z < 65536, "conv1d: grid too large");
         // staggered start (RVC_X6_STAGGER shader cycles) when the launch runs more than one round of blocks per CU
@@ -1827,6 +2081,15 @@ extern "C" int rvc_conv1d_engine(const rvc_conv1d_args* a) {
     size_t lds;
     if (plan(a, p, cfg, grid, lds) != RVC_OK) return -1;
     return cfg.x6 ? 1 : 0;
+}
+
+extern "C" int rvc_conv1d_tile(const rvc_conv1d_args* a) {
+    ConvParams p;
+    Cfg cfg;
+    dim3 grid;
+    size_t lds;
+    if (plan(a, p, cfg, grid, lds) != RVC_OK) return -1;
+    return (16 * cfg.FM * cfg.WM) << 16 | (16 * cfg.FN * cfg.WN);
 }
 
 extern "C" int64_t rvc_conv1d_workspace_bytes(const rvc_conv1d_args* a) {

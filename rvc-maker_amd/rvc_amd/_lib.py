@@ -142,6 +142,7 @@ SIGNATURES = {
     "rvc_stream_create_cu_mask": [c_void_p, c_int, POINTER(c_void_p)],
     "rvc_stream_destroy": [c_void_p],
     "rvc_conv1d_engine": [POINTER(Conv1dArgs)],
+    "rvc_conv1d_tile": [POINTER(Conv1dArgs)],
     "rvc_conv1d_x6_bytes": [c_int64, c_int64, c_int, c_int64],
     "rvc_conv1d_pack_x6": [c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, POINTER(c_int), c_void_p],
     "rvc_conv1d_f16_bytes": [c_int64, c_int64, c_int, c_int64],

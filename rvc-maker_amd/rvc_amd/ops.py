@@ -244,8 +244,17 @@ LAST_CONV_FLOPS = 0.0
 LAST_CONV_ENGINE = 0  # 0 = f32 MFMA engine, 1 = split-bf16 (x6) engine
 LAST_CONV_PASSES = 0  # the split-operand launch's pass set (PASSES values; F16X3 = split-fp16), 0 = f32 engine
 LAST_CONV_WS = 0  # its split-K workspace bytes (0 = not split)
+_LAST_CONV_ARGS = None  # its argument block, for last_conv_tile()
 _WS = {}
 _WS_PRIVATE = None  # a workspace store owned by a captured graph (private_workspaces)
+
+
+def last_conv_tile():
+    """The (rows, columns) output tile the last conv1d launch's blocks computed (rvc_conv1d_tile: the plan for its
+    arguments under the current switches; asked on demand, so a launch pays nothing for it)."""
+    if _LAST_CONV_ARGS is None:
+        return 0, 0
+    return divmod(_lib.load().rvc_conv1d_tile(ctypes.byref(_LAST_CONV_ARGS)), 1 << 16)
 
 
 class private_workspaces:
@@ -311,7 +320,7 @@ def conv1d(x, w, Ci, Co, K, *, bias=None, bias2=None, stride=1, pad=0, dil=1, gr
 
     ``flops`` is the launch's ALGORITHMIC FLOP count for roofline accounting (recorded in
     LAST_CONV_FLOPS); the default is 2*B*Co*(Ci/g)*K*(valid outputs)."""
-    global LAST_CONV_FLOPS, LAST_CONV_ENGINE, LAST_CONV_PASSES, LAST_CONV_WS
+    global LAST_CONV_FLOPS, LAST_CONV_ENGINE, LAST_CONV_PASSES, LAST_CONV_WS, _LAST_CONV_ARGS
     if B is None:
         B, Cx, Lx = _shape3(x)
         if Lin is None:
@@ -383,6 +392,7 @@ def conv1d(x, w, Ci, Co, K, *, bias=None, bias2=None, stride=1, pad=0, dil=1, gr
     LAST_CONV_WS = need
     LAST_CONV_ENGINE = lib.rvc_conv1d_engine(ctypes.byref(a))
     LAST_CONV_PASSES = a.wx_passes if LAST_CONV_ENGINE == 1 else 0
+    _LAST_CONV_ARGS = a
     check(lib.rvc_conv1d(ctypes.byref(a), _p(ws), need, _stream()), "conv1d")
     return out
 

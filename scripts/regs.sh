@@ -1,8 +1,17 @@
 #!/bin/bash
-# Per-kernel register / occupancy summary of a HIP source for gfx950: scripts/regs.sh file.hip
+# Per-kernel register / occupancy summary of a HIP source for gfx950, compiled device-only with the flags of
+# csrc/Makefile (its CXXFLAGS with the default ARCH; EXTRA from the environment): scripts/regs.sh file.hip
 f=${1:?usage: regs.sh file.hip}
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -I"$(dirname "$0")/../rvc-maker_amd/csrc" -c "$f" \
-  -o /tmp/regs_$$.o -Rpass-analysis=kernel-resource-usage 2>&1 |
+root="$(cd "$(dirname "$0")/.." && pwd)"
+mk="$root/rvc-maker_amd/csrc/Makefile"
+hipcc=$(command -v hipcc || echo /opt/rocm/bin/hipcc)
+arch=$(sed -n 's/^ARCH ?= //p' "$mk")
+flags=$(sed -n 's/^CXXFLAGS := //p' "$mk")
+flags=${flags//\$(ARCH)/$arch}
+flags=${flags//\$(EXTRA)/$EXTRA}
+tmp=$(mktemp -d)
+# shellcheck disable=SC2086
+"$hipcc" $flags --cuda-device-only -S "$f" -o "$tmp/regs.s" -Rpass-analysis=kernel-resource-usage 2>&1 |
   python3 -c '
 import re, sys
 rows, cur = [], None
@@ -15,4 +24,4 @@ for line in sys.stdin:
 for r in rows:
     print(r["name"][:80].ljust(80), "V", r.get("VGPRs"), "A", r.get("AGPRs"), "spill", r.get("VGPRsS"),
           "scratch", r.get("ScratchSize"), "occ", r.get("Occupancy"))'
-rm -f /tmp/regs_$$.o
+rm -rf "$tmp"

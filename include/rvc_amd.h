@@ -505,6 +505,67 @@ int rvc_pm_windows(double* window, double* window_r);
 int rvc_pm_post(const double* f0, int64_t nf, int64_t p_len, double shift, const rvc_f0_post* post,
                 int64_t* coarse, float* pitchf, rvc_stream_t stream);
 
+/* swipe f0 (VC.get_f0_swipe, convert.py:272-276: SWIPE' at 16 kHz, 50..1100 Hz, 10 ms frames, strength
+ * threshold 0.3), f64 on the f32 samples.  rvc_swipe_tables builds, on the HOST (host pointer), the constant
+ * blob of rvc_swipe_tables_bytes() bytes that the device entries take as `tables` once it is uploaded.
+ * rvc_swipe_table_dims(which, window, dims) returns the byte offset of one table in the blob and writes
+ * dims = {rows, cols, leading dimension}; `window` (0..4 = window size 2048 >> window) selects among the
+ * per-window tables and is ignored by the others.
+ *   rvc_swipe_strength  x f32 [n] -> S f64 [429][rvc_swipe_frames(n)]; work: rvc_swipe_work_bytes(n) bytes
+ *   rvc_swipe_pick      S [429][F] -> f0 f32 [F] (0 = unvoiced)
+ *   rvc_swipe_post      get_f0's autotune / shift / f0 file (post, as rvc_rmvpe_decode) and mel quantiser
+ *                       in f32 arithmetic -> coarse, pitchf [F]
+ * No entry synchronises or allocates. */
+enum {
+    RVC_SWIPE_PC = 0,    /* f64 [429] pitch candidates */
+    RVC_SWIPE_FERBS = 1, /* f64 [328] ERB-spaced frequencies */
+    RVC_SWIPE_IDX = 2,   /* int32 [nc_w] the candidates window w serves */
+    RVC_SWIPE_MU = 3,    /* f64 [nc_w] their weights */
+    RVC_SWIPE_W = 4,     /* f64 [328][ws/2 + 1] (ld: padded to 16) not-a-knot cubic spline onto fERBs */
+    RVC_SWIPE_K = 5,     /* f64 [nc_w][328] (ld 336) prime-harmonic cosine kernels */
+    RVC_SWIPE_WIN = 6,   /* f64 [ws + 1] np.hanning(ws + 2)[1:-1], then its sum */
+    RVC_SWIPE_TW = 7,    /* f64 [1024][2] exp(-2 pi i k / 2048) */
+    RVC_SWIPE_CMAP = 8,  /* int32 [429][2][2] (window, index in it) of the windows serving a candidate; -1 none */
+    RVC_SWIPE_CMU = 9,   /* f64 [429][2] their weights */
+    RVC_SWIPE_PX = 10,   /* f64 [429][2] the pick parabola's outer abscissae */
+    RVC_SWIPE_GRIDX = 11,  /* f64 [429][17] the pick grid's abscissae */
+    RVC_SWIPE_GRIDF0 = 12, /* f32 [429][17] the f0 each grid point stands for */
+    /* W and K again as the kernels read them, in MFMA operand order: [row tile][K/16][lane 0..63][u 0..3] =
+     * M[16 tile + (lane & 15)][4 (4 k16 + u) + (lane >> 4)] over the zero-padded matrix (dims: tiles x K*16) */
+    RVC_SWIPE_WP = 13,
+    RVC_SWIPE_KP = 14
+};
+int64_t rvc_swipe_frames(int64_t n);     /* n / 160 + 1; -1 for n <= 0 */
+int64_t rvc_swipe_work_bytes(int64_t n); /* -1 for n <= 0 or n >= 2^30 */
+int64_t rvc_swipe_tables_bytes(void);
+int64_t rvc_swipe_table_dims(int which, int window, int64_t* dims);
+int rvc_swipe_tables(void* blob, int64_t bytes);
+int rvc_swipe_strength(const float* x, int64_t n, const void* tables, void* work, int64_t work_bytes, double* S,
+                       rvc_stream_t stream);
+int rvc_swipe_pick(const double* S, int64_t F, const void* tables, float* f0, rvc_stream_t stream);
+int rvc_swipe_post(const float* f0, int64_t F, float shift, const rvc_f0_post* post, int64_t* coarse,
+                   float* pitchf, rvc_stream_t stream);
+
+/* hybrid[a+b+...] f0 (VC.get_f0_hybrid, convert.py:283-302).
+ *   rvc_abs_quantile  np.quantile(np.abs(x), 0.999) of f32 x [n] -> device f32 scalar q_out, as NumPy 2
+ *                     evaluates it for an f32 array (index, gamma and lerp in f32); a radix select, no sort;
+ *                     work: rvc_abs_quantile_work_bytes() bytes of device memory
+ *   rvc_div_scalar    out[i] = x[i] / q[0], a true f32 division by the device scalar (out may be x)
+ *   rvc_f0_mix        M <= RVC_F0_MIX_MAX raw tracks (device f32 or f64, each with its own length) -> out f64
+ *                     [p_len]: np.interp(np.linspace(0, n_m, p_len), np.arange(n_m), f0_m) in f64 per track,
+ *                     then np.nanmedian over the tracks (one track: the resampled track).  p_len >= 2.
+ * The mixed track's autotune / shift / f0 file / quantiser is rvc_pm_post with nf = p_len. */
+enum { RVC_F0_MIX_MAX = 8 };
+typedef struct rvc_f0_track {
+    const void* f0; /* device f32 or f64 [n] */
+    int64_t n;
+    int is_f64, _pad0;
+} rvc_f0_track;
+int64_t rvc_abs_quantile_work_bytes(void);
+int rvc_abs_quantile(const float* x, int64_t n, void* work, int64_t work_bytes, float* q_out, rvc_stream_t stream);
+int rvc_div_scalar(const float* x, int64_t n, const float* q, float* out, rvc_stream_t stream);
+int rvc_f0_mix(const rvc_f0_track* tracks, int M, int64_t p_len, double* out, rvc_stream_t stream);
+
 /* ------------------------------------------------------------------ VC.pipeline glue
  * phone_upsample: nearest x2 + protect blend (convert.py:361-378) -> phone [C][T]
  * peak_normalize: x /= max|x|/0.99 when > 1 (convert.py:450-451); ws: 16 B scratch;

@@ -67,6 +67,11 @@ class F0Post(ctypes.Structure):
                 ("rep_off", c_int64), ("rep_len", c_int64)]
 
 
+class F0Track(ctypes.Structure):
+    """rvc_f0_track: one raw member track of a hybrid[...] f0 mix."""
+    _fields_ = [("f0", c_void_p), ("n", c_int64), ("is_f64", c_int), ("_pad0", c_int)]
+
+
 class ResblockArgs(ctypes.Structure):
     """rvc_resblock_args: one fused (convs1[i], convs2[i]) ResBlock pair (residuals.py:22-44)."""
     _fields_ = [("x", c_void_p), ("y", c_void_p), ("w1x", c_void_p), ("b1", c_void_p), ("w2x", c_void_p),
@@ -150,6 +155,18 @@ SIGNATURES = {
     "rvc_pm_work_bytes": [c_int64],
     "rvc_pm_f0": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
     "rvc_pm_post": [c_void_p, c_int64, c_int64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p],
+    "rvc_swipe_frames": [c_int64],
+    "rvc_swipe_work_bytes": [c_int64],
+    "rvc_swipe_tables_bytes": [],
+    "rvc_swipe_table_dims": [c_int, c_int, POINTER(c_int64)],
+    "rvc_swipe_tables": [c_void_p, c_int64],
+    "rvc_swipe_strength": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
+    "rvc_swipe_pick": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    "rvc_swipe_post": [c_void_p, c_int64, c_float, POINTER(F0Post), c_void_p, c_void_p, c_void_p],
+    "rvc_abs_quantile_work_bytes": [],
+    "rvc_abs_quantile": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
+    "rvc_div_scalar": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    "rvc_f0_mix": [POINTER(F0Track), c_int, c_int64, c_void_p, c_void_p],
     "rvc_conv1d_pack_f16": [c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, POINTER(c_int), c_void_p],
     "rvc_attention_workspace_bytes": [POINTER(AttnArgs)],
     "rvc_attention": [POINTER(AttnArgs), c_void_p, c_int64, c_void_p],
@@ -287,7 +304,9 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_vc_out_len": c_int64, "rvc_device_bytes_in_use": c_int64,
              "rvc_quiet_points_count": c_int64, "rvc_f0_file_resample": c_int64, "rvc_quiet_points_ws_bytes": c_int64,
              "rvc_fe0_ws_bytes": c_int64, "rvc_harmonic_source_ws_bytes": c_int64,
-             "rvc_harmonic_source_chunk": c_int64}
+             "rvc_harmonic_source_chunk": c_int64, "rvc_swipe_frames": c_int64, "rvc_swipe_work_bytes": c_int64,
+             "rvc_swipe_tables_bytes": c_int64, "rvc_swipe_table_dims": c_int64,
+             "rvc_abs_quantile_work_bytes": c_int64}
 
 _lib = None
 

@@ -14,8 +14,9 @@ files are the only output, so there is no data-path collective, only a barrier b
 the file list.  Host-side steps (coarse quantiser, file naming, list building) follow the reference
 expression for expression; ``tests/golden/edges.npz`` pins ``coarse_f0`` against it.
 
-f0 methods on the device: ``rmvpe`` and ``crepe-{tiny,...,full}`` (the reference's other estimators
--- pm, harvest, fcpe, ... -- are third-party or off the path and raise).  Embedders: fairseq
+f0 methods on the device: ``rmvpe``, ``crepe-{tiny,...,full}``, ``swipe`` and ``hybrid[a+b+...]`` over
+those and ``pm`` (the reference's other estimators -- harvest, fcpe, yin, ... -- are third-party or off
+the path and raise).  Embedders: fairseq
 ContentVec (``embedders_mode="fairseq"``).
 """
 from __future__ import annotations
@@ -51,8 +52,12 @@ class FeatureInputAMD:
     def compute_f0(self, np_arr, f0_method, hop_length=160, f0_onnx=False):
         """extract.py:149-151 for the device methods: rmvpe -> f64 [1 + N//160] (RMVPE.infer_from_audio,
         thred 0.03); crepe-<cap> -> f32 [1 + N//160] (get_crepe, :173-180)."""
-        if f0_onnx or "hybrid" in f0_method:
-            raise NotImplementedError(f"f0 method {f0_method!r} (onnx / hybrid) is not on the device path")
+        if f0_onnx:
+            raise NotImplementedError(f"f0 method {f0_method!r} (onnx) is not on the device path")
+        if "hybrid" in f0_method:
+            return self.compute_f0_hybrid(f0_method, np_arr)
+        if f0_method == "swipe":  # get_swipe (:212-216): f32 [1 + N//160]
+            return self._swipe().f0(self._dev32(np_arr)).cpu().numpy()
         if f0_method == "rmvpe":
             if self.rmvpe is None:
                 from .rmvpe import RMVPEAMD
@@ -68,7 +73,39 @@ class FeatureInputAMD:
             x = torch.from_numpy(np.copy(np_arr).astype(np.float32)).to(self.device)
             _, f0 = self.crepe[cap].f0_device(x, 0.0)
             return f0.cpu().numpy()
-        raise NotImplementedError(f"f0 method {f0_method!r}: only rmvpe and crepe-* are on the device path")
+        raise NotImplementedError(f"f0 method {f0_method!r}: only rmvpe, crepe-*, swipe and hybrid[...] over "
+                                  "rmvpe, crepe-*, pm and swipe are on the device path")
+
+    def _dev32(self, np_arr):
+        return torch.from_numpy(np.copy(np_arr).astype(np.float32)).to(self.device)
+
+    def _swipe(self):
+        if getattr(self, "swipe", None) is None:
+            from .swipe import SwipeAMD
+            self.swipe = SwipeAMD(self.device)
+        return self.swipe
+
+    def compute_f0_hybrid(self, f0_method, np_arr):
+        """extract.py:132-147: the members' raw tracks on the signal as it is (no quantile normalisation, unlike
+        the conversion path), each resampled to N // hop frames, then their nanmedian: f64 [N // hop]."""
+        from . import f0mix
+        p_len = np_arr.size // self.hop
+        tracks = []
+        for member in f0mix.parse_hybrid(f0_method):
+            if member == "pm":  # get_pm (:153-160): Praat on the f64 samples, zero-padded to N // hop
+                if getattr(self, "pm", None) is None:
+                    from .pm import PitchPM
+                    self.pm = PitchPM(self.device)
+                f0 = self.pm.to_pitch_ac(torch.from_numpy(np.asarray(np_arr, np.float64)).to(self.device))
+                pad = (p_len - f0.numel() + 1) // 2
+                if pad > 0 or p_len - f0.numel() - pad > 0:
+                    f0 = torch.nn.functional.pad(f0, (pad, p_len - f0.numel() - pad))
+            elif member == "swipe":
+                f0 = self._swipe().f0(self._dev32(np_arr))
+            else:  # rmvpe f64, crepe-* f32, as compute_f0 returns them
+                f0 = torch.from_numpy(np.ascontiguousarray(self.compute_f0(np_arr, member))).to(self.device)
+            tracks.append(f0)
+        return f0mix.mix(tracks, p_len).cpu().numpy()
 
     def coarse_f0(self, f0):
         """extract.py:225-226 (numpy, same expression and dtype promotion)."""

@@ -28,6 +28,8 @@ class ClipGraph:
         if n_samples + vc.window > vc.t_max:
             raise ValueError(f"ClipGraph: a {n_samples}-sample clip is segmented on the host (> t_max); "
                              "split it into chunks first")
+        if "hybrid" in f0_method:
+            raise NotImplementedError("ClipGraph: hybrid[...] f0 is not captured; use pipeline_device")
         self.vc = vc
         dev = torch.device(vc.device)
         self.n = int(n_samples)

@@ -17,7 +17,9 @@ releases the streams the library created for it.
 FAISS retrieval (``file_index`` + ``index_rate``) runs on the device (retrieval.py / ivf.hip); the
 index file is read without faiss (faiss_index.py) and kept resident per path.
 
-f0 methods: "rmvpe" and "crepe-{tiny,small,medium,large,full}" (crepe.py), both on the device.
+f0 methods, all on the device: "rmvpe", "crepe-{tiny,small,medium,large,full}" (crepe.py), "pm" (pm.py),
+"swipe" (swipe.py) and "hybrid[a+b+...]" over those (f0mix.py: the members' raw tracks resampled and their
+nanmedian taken, as get_f0_hybrid).
 
 f0 autotune and f0 files run inside the f0 decode kernels; volume_envelope != 1 (change_rms) runs on
 the device after the segment loop.  Embedders: fairseq ``.pt`` and transformers ``.safetensors``
@@ -33,8 +35,9 @@ import numpy as np
 import torch
 from scipy import signal
 
+from . import _lib
 from . import contentvec as cvm
-from . import ops
+from . import f0mix, ops
 
 BH, AH = signal.butter(N=5, Wn=48, btype="high", fs=16000)  # convert.py:30
 
@@ -168,7 +171,56 @@ class VC:
                 from .pm import PitchPM
                 self.pm = PitchPM(xp64.device)
             return self.pm.f0_device(xp64, xp.numel() // self.window, float(pitch), post=post)
-        raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-* and pm are on the MI355X path")
+        if f0_method == "swipe":
+            # get_f0_swipe reads x.astype(np.float32) of the f64 filtered signal: xp is that rounding already
+            # (filtfilt.hip's filt_reflect_pad stores (float)v beside the f64 v)
+            return self._swipe(xp.device).f0_device(xp.contiguous(), float(pitch), post=post)
+        if f0mix.is_hybrid(f0_method):
+            return self._f0_hybrid(xp, float(pitch), f0mix.parse_hybrid(f0_method), post)
+        raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe and hybrid[...] over them "
+                                  "are on the MI355X path")
+
+    def _swipe(self, device):
+        if getattr(self, "swipe", None) is None:
+            from .swipe import SwipeAMD
+            self.swipe = SwipeAMD(device)
+        return self.swipe
+
+    def f0_raw(self, x32, member, p_len):
+        """One estimator's raw track (before any shift / autotune) on the device f32 signal x32, as
+        get_f0_hybrid's members return it: rmvpe f64 [1 + N//160], crepe-* f32 [1 + N//160], pm f64 padded to
+        p_len, swipe f32 [1 + N//160]."""
+        if member == "rmvpe":
+            return self._rmvpe().f0_device(x32, 0.03, 0.0, want_f0=True)[2]
+        if member in self.CREPE_METHODS:
+            # shift 2^0 = 1 and no post: pitchf is the raw f0
+            return self._crepe(self.CREPE_METHODS[member]).f0_device(x32, 0.0)[1]
+        if member == "pm":
+            if getattr(self, "pm", None) is None:
+                from .pm import PitchPM
+                self.pm = PitchPM(x32.device)
+            f0 = self.pm.to_pitch_ac(x32.double())
+            pad = (p_len - f0.numel() + 1) // 2  # get_f0_pm's padding (convert.py:210-212)
+            if pad > 0 or p_len - f0.numel() - pad > 0:
+                f0 = torch.nn.functional.pad(f0, (pad, p_len - f0.numel() - pad))
+            return f0
+        if member == "swipe":
+            return self._swipe(x32.device).f0(x32)
+        raise NotImplementedError(f"hybrid f0 member {member!r}: rmvpe, crepe-*, pm and swipe are on the MI355X path")
+
+    def _f0_hybrid(self, xp, pitch, members, post):
+        """get_f0_hybrid + get_f0's post (convert.py:283-323): every member reads the f32 signal divided by its
+        0.999 |x| quantile; the raw tracks are resampled to p_len and their nanmedian taken, in f64."""
+        from . import pm as _pm
+        p_len = xp.numel() // self.window
+        xn = f0mix.normalize(xp.contiguous())
+        f0 = f0mix.mix([self.f0_raw(xn, m, p_len) for m in members], p_len)
+        coarse = torch.empty(p_len, dtype=torch.int64, device=xp.device)
+        pitchf = torch.empty(p_len, device=xp.device)
+        ops.check(_lib.load().rvc_pm_post(_pm._p64(f0), p_len, p_len, float(2.0 ** (pitch / 12)),
+                                          ops._post_ref(post, p_len), ops._p(coarse), ops._p(pitchf), ops._stream()),
+                  "pm_post")
+        return coarse, pitchf
 
     # ------------------------------------------------------------------ device pieces
     def features_device(self, model, a0, version):
@@ -660,8 +712,13 @@ class VC:
     def pipeline(self, model, net_g, sid, audio, pitch, f0_method, file_index, index_rate, pitch_guidance,
                  filter_radius, volume_envelope, version, protect, hop_length, f0_autotune, f0_autotune_strength,
                  suffix, embed_suffix, f0_file=None, f0_onnx=False, pbar=None):
-        if (f0_method not in ("rmvpe", "pm") and f0_method not in self.CREPE_METHODS) or f0_onnx:
-            raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-* and pm are on the MI355X path")
+        if f0_onnx:
+            raise NotImplementedError("f0_onnx: ONNX f0 models are not on the MI355X path")
+        if f0mix.is_hybrid(f0_method):
+            f0mix.parse_hybrid(f0_method)  # raises, naming the member, for one that is not on the device path
+        elif f0_method not in ("rmvpe", "pm", "swipe") and f0_method not in self.CREPE_METHODS:
+            raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe and hybrid[...] over "
+                                      "them are on the MI355X path")
         index = None
         if file_index != "" and os.path.exists(file_index) and index_rate != 0:  # convert.py:392-399
             index = self._index(file_index)

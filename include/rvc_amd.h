@@ -623,6 +623,31 @@ int64_t rvc_denoise_work_bytes(int64_t n, const rvc_denoise_args* a);
 int rvc_denoise(const float* y, int64_t n, const rvc_denoise_args* a, void* work, int64_t work_bytes, float* out,
                 rvc_stream_t stream);
 
+/* ------------------------------------------------------------------ formant shifting
+ * Replaces StftPitchShift(n_fft, hop, sample_rate).shiftpitch(x, factors=1, quefrency, distortion)
+ * (main/library/algorithm/stftpitchshift.py) as load_audio calls it for formant_shifting
+ * (main/library/utils.py:104-108): a phase vocoder at factor 1 whose cepstral envelope is resampled
+ * along frequency by `distortion`, in f64 like the reference.  M = (n - n_fft) / hop + 1 frames, no
+ * centre padding; the tail the frames do not reach is exactly 0.
+ *   n_fft: a power of two in [64, 2048] (the reference's call: 1024); hop in [1, n_fft] (32);
+ *   quefrency_samples = int(quefrency * sample_rate), in [0, n_fft / 2]; 0 skips the lifter and
+ *     `distortion` with it;
+ *   distortion: finite, > 0, int((n_fft / 2 + 1) * distortion) >= 1; 1 leaves the envelope in place;
+ *   window:       device f64 [n_fft] = 0.5 - 0.5 cos(2 pi i / n_fft);
+ *   synth_window: device f64 [n_fft] = window * hop / sum(window^2).
+ * x f32 [n] -> out f32 [n]; work: rvc_formant_work_bytes(n, a) bytes of device scratch (-1 on bad
+ * arguments).  Stream-ordered, no host synchronisation, no atomics (bit-reproducible). */
+typedef struct rvc_formant_args {
+    int n_fft, hop, sample_rate, quefrency_samples;
+    double distortion;
+    const double* window;
+    const double* synth_window;
+} rvc_formant_args;
+
+int64_t rvc_formant_work_bytes(int64_t n, const rvc_formant_args* a);
+int rvc_formant_shift(const float* x, int64_t n, const rvc_formant_args* a, void* work, int64_t work_bytes, float* out,
+                      rvc_stream_t stream);
+
 /* ------------------------------------------------------------------ FAISS IVF-Flat retrieval
  * Replaces faiss IndexIVFFlat(L2).search(feats, k=8) + the blend of convert.py:349-359.
  * Queries (query i, dim c) live at q[c*cs + i*qs] (channels-first [d][nq]: cs = nq, qs = 1).

@@ -87,6 +87,12 @@ class DenoiseArgs(ctypes.Structure):
                 ("window", c_void_p), ("filt", c_void_p)]
 
 
+class FormantArgs(ctypes.Structure):
+    """rvc_formant_args: StftPitchShift.shiftpitch at factor 1 (main/library/algorithm/stftpitchshift.py)."""
+    _fields_ = [("n_fft", c_int), ("hop", c_int), ("sample_rate", c_int), ("quefrency_samples", c_int),
+                ("distortion", c_double), ("window", c_void_p), ("synth_window", c_void_p)]
+
+
 class Param(ctypes.Structure):
     """rvc_param: one named host array of a checkpoint's weight dict (model-level API)."""
     _fields_ = [("name", ctypes.c_char_p), ("data", c_void_p), ("dtype", c_int), ("ndim", c_int),
@@ -262,6 +268,8 @@ SIGNATURES = {
     "rvc_resblock_lds_bytes": [c_int64, c_int, c_int, c_int],
     "rvc_resblock_pair": [POINTER(ResblockArgs), c_void_p],
     "rvc_denoise": [c_void_p, c_int64, POINTER(DenoiseArgs), c_void_p, c_int64, c_void_p, c_void_p],
+    "rvc_formant_work_bytes": [c_int64, POINTER(FormantArgs)],
+    "rvc_formant_shift": [c_void_p, c_int64, POINTER(FormantArgs), c_void_p, c_int64, c_void_p, c_void_p],
     "rvc_ctx_create": [c_int, POINTER(c_void_p)],
     "rvc_ctx_destroy": [c_void_p],
     "rvc_ctx_set_precision": [c_void_p, c_int],
@@ -306,7 +314,7 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_fe0_ws_bytes": c_int64, "rvc_harmonic_source_ws_bytes": c_int64,
              "rvc_harmonic_source_chunk": c_int64, "rvc_swipe_frames": c_int64, "rvc_swipe_work_bytes": c_int64,
              "rvc_swipe_tables_bytes": c_int64, "rvc_swipe_table_dims": c_int64,
-             "rvc_abs_quantile_work_bytes": c_int64}
+             "rvc_abs_quantile_work_bytes": c_int64, "rvc_formant_work_bytes": c_int64}
 
 _lib = None
 

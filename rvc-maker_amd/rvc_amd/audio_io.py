@@ -1,6 +1,6 @@
 """Audio file I/O for the edges of the path (``main/library/utils.py:89-112`` load_audio,
 ``convert.py:518`` sf.write, ``extract.py:91-100`` read_wave), without soundfile / librosa / soxr
-(none is in this image).
+(none is in this image).  ``load_audio``'s formant shifting runs on the device (``rvc_amd.formant``).
 
 * WAV is read and written with ``scipy.io.wavfile``.  Integer PCM is scaled to f32 the way
   libsndfile does for ``dtype=float32`` (x / 2^(bits-1)); multi-channel input is averaged to mono
@@ -41,8 +41,11 @@ def resample(x: np.ndarray, orig_sr: int, target_sr: int) -> np.ndarray:
     return signal.resample_poly(x, target_sr // g, orig_sr // g, axis=-1).astype(np.float32)
 
 
-def load_audio(file: str, sample_rate: int = 16000) -> np.ndarray:
-    """utils.py:89-112 without formant shifting: mono f32 at ``sample_rate``, flattened."""
+def load_audio(file: str, sample_rate: int = 16000, formant_shifting: bool = False, formant_qfrency: float = 0.8,
+               formant_timbre: float = 0.8, device: str = "cuda") -> np.ndarray:
+    """utils.py:89-112: mono f32 at ``sample_rate``, flattened.  With ``formant_shifting`` the resampled audio
+    goes through the device formant shifter (rvc_amd.formant; utils.py:104-108), whose failure is re-raised as
+    RuntimeError like every failure of the reference's load."""
     file = file.strip(" ").strip('"').strip("\n").strip('"').strip(" ")
     if not os.path.isfile(file):
         raise FileNotFoundError(file)
@@ -51,6 +54,13 @@ def load_audio(file: str, sample_rate: int = 16000) -> np.ndarray:
         audio = audio.mean(axis=1, dtype=np.float32)
     if sr != sample_rate:
         audio = resample(audio, sr, sample_rate)
+    if formant_shifting:
+        from .formant import shiftpitch
+        try:
+            audio = shiftpitch(audio, factors=1, quefrency=formant_qfrency * 1e-3, distortion=formant_timbre,
+                               framesize=1024, hopsize=32, samplerate=sample_rate, device=device)
+        except Exception as e:  # noqa: BLE001 -- utils.py:110-111
+            raise RuntimeError(f"load_audio: formant shifting failed: {e}") from e
     return audio.flatten()
 
 

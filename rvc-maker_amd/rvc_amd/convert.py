@@ -6,8 +6,10 @@ nearest standard rate, write.
 Batch mode shards the files over ranks (one process per GPU, longest file first to the least-loaded
 rank -- shard.shard_utterances); each rank writes its own outputs, so no waveform crosses ranks.
 
-``clean_audio`` runs the spectral gate of main/tools/noisereduce.py on the device (rvc_amd.denoise).
-Not on the device path (raise): formant shifting, non-WAV export.
+``clean_audio`` runs the spectral gate of main/tools/noisereduce.py on the device (rvc_amd.denoise);
+``formant_shifting`` runs the phase vocoder of main/library/algorithm/stftpitchshift.py on the device
+inside ``load_audio`` (rvc_amd.formant), before the peak limit.
+Not on the device path (raise): non-WAV export.
 Resampling (input != 16 kHz, or a model rate that is not a standard rate) is parity-unpinned
 (audio_io module note).
 """
@@ -52,15 +54,15 @@ class VoiceConverterAMD:
         """convert.py:479-523.  Like the reference, errors are logged and the call returns None;
         on success the written waveform is returned."""
         try:
-            if formant_shifting:
-                raise NotImplementedError("formant shifting is not on the MI355X path")
             if export_format != "wav":
                 raise NotImplementedError("only WAV export (no soundfile / ffmpeg in this build)")
             embed_suffix = embed_suffix_of(embedders_mode)
             if embed_suffix != self.embed_suffix:
                 raise ValueError(f"embedders_mode {embedders_mode!r} reads a {embed_suffix} embedder, but the loaded "
                                  f"model is a {self.embed_suffix} one")
-            audio = audio_io.load_audio(audio_input_path, self.sample_rate)
+            audio = audio_io.load_audio(audio_input_path, self.sample_rate, formant_shifting=formant_shifting,
+                                        formant_qfrency=formant_qfrency, formant_timbre=formant_timbre,
+                                        device=self.vc.device)
             audio_max = np.abs(audio).max() / 0.95
             if audio_max > 1:
                 audio /= audio_max

@@ -294,16 +294,19 @@ __global__ __launch_bounds__(256) void rms_frames_kernel(const double* y64, cons
 }
 
 // torch F.interpolate(mode="linear", align_corners=False) of r [m] to n points, at output index i.
+// torch's CPU kernel is built with FMA (its AVX2 / AVX512 dispatch): the source index is one fused
+// scale * (i + 0.5) - 0.5 and the blend fma(l0, r[i0], l1 * r[i1]).  Next to a silent frame the weight 1 - l1 is
+// small and a separately rounded index moves the result by up to 3e-4 relative, so both are fused here, explicitly.
 __device__ __forceinline__ float interp_linear(const float* r, int64_t m, int64_t n, int64_t i) {
 #pragma clang fp contract(off)
     const float scale = (float)m / (float)n;
-    float src = scale * ((float)i + 0.5f) - 0.5f;
+    float src = fmaf(scale, (float)i + 0.5f, -0.5f);
     if (src < 0.f) src = 0.f;
     int64_t i0 = (int64_t)src;
     if (i0 > m - 1) i0 = m - 1;
     const int64_t i1 = i0 + (i0 < m - 1 ? 1 : 0);
     const float l1 = src - (float)i0, l0 = 1.f - l1;
-    return l0 * r[i0] + l1 * r[i1];
+    return fmaf(l0, r[i0], l1 * r[i1]);
 }
 
 __global__ __launch_bounds__(256) void rms_mix_kernel(float* y, int64_t n, const float* r1, int64_t n1, const float* r2,

@@ -673,6 +673,34 @@ int rvc_ivf_blend(const float* feats, int64_t nq, int64_t d, int64_t fcs, int64_
                   int k, const float* big, int64_t ntotal, double index_rate, float* out, int64_t ocs, int64_t oqs,
                   rvc_stream_t stream);
 
+/* ------------------------------------------------------------------ IVF training (kmeans.hip)
+ * The device side of create_index.py:66-83 (index_factory("IVF{n},Flat"), train, add): faiss's k-means steps and the
+ * inverted lists.  The iteration loop, the initial permutation and the split of empty clusters are host control
+ * (rvc_amd/index_train.py).  Every entry point validates before any launch (d % 8 == 0, 8 <= d <= 1024, as
+ * rvc_load_index), runs on the given stream, allocates nothing, never synchronises with the host and uses no
+ * floating-point atomics: two runs give identical bits.  x [n][d], cent [k][d]: row-major f32, 16-byte aligned.
+ *
+ * rvc_kmeans_assign: the nearest centroid of every row, 1 <= k <= n.  The decision value is ||c_j||^2 - 2 <x_i, c_j>
+ *   in f32, the inner products on v_mfma_f32_32x32x2_f32 (exact f32 products, one f32 fma chain over the dimensions
+ *   in order); equal values resolve to the lowest j.  assign int32 [n]; dist f32 [n] = that value + ||x_i||^2,
+ *   clamped at 0.  The [n][k] matrix is never written.  work: rvc_kmeans_assign_work_bytes(n, d, k) bytes.
+ * rvc_kmeans_lists: stable counting sort of the row numbers by list: counts int32 [k], list_off int64 [k + 1] (CSR),
+ *   ids int64 [n] ascending inside each list, as faiss's sequential add leaves them.  assign values outside [0, k)
+ *   are clamped.  work: rvc_kmeans_lists_work_bytes(n, k) bytes.
+ * rvc_kmeans_update: faiss compute_centroids: per centroid and dimension the f32 sum of the members in ascending
+ *   list position from 0, times 1.f / count (f32); an empty list copies cent_prev.  cent_out != cent_prev.
+ * rvc_gather_rows: out [m][d] = x[ids[i]] (ids int64, the caller guarantees their range).
+ * The *_work_bytes queries return -1 on bad sizes. */
+int64_t rvc_kmeans_assign_work_bytes(int64_t n, int64_t d, int64_t k);
+int rvc_kmeans_assign(const float* x, int64_t n, int64_t d, const float* cent, int64_t k, void* work,
+                      int64_t work_bytes, int32_t* assign, float* dist, rvc_stream_t stream);
+int64_t rvc_kmeans_lists_work_bytes(int64_t n, int64_t k);
+int rvc_kmeans_lists(const int32_t* assign, int64_t n, int64_t k, void* work, int64_t work_bytes, int64_t* list_off,
+                     int64_t* ids, int32_t* counts, rvc_stream_t stream);
+int rvc_kmeans_update(const float* x, int64_t n, int64_t d, const int64_t* list_off, const int64_t* ids, int64_t k,
+                      const float* cent_prev, float* cent_out, rvc_stream_t stream);
+int rvc_gather_rows(const float* x, int64_t d, const int64_t* ids, int64_t m, float* out, rvc_stream_t stream);
+
 /* ------------------------------------------------------------------ CREPE f0 (VC.get_f0_crepe, convert.py:230-237)
  * crepe_frames: CREPE.py:151-171 framing (1024 @ hop, 512 zero pad) + per-frame zero-mean / unbiased-std
  *   normalisation of frames [frame0, frame0 + nframes) -> out [nframes][1024].

@@ -251,6 +251,13 @@ SIGNATURES = {
                        c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "rvc_ivf_blend": [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64,
                       c_double, c_void_p, c_int64, c_int64, c_void_p],
+    "rvc_kmeans_assign_work_bytes": [c_int64, c_int64, c_int64],
+    "rvc_kmeans_assign": [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                          c_void_p],
+    "rvc_kmeans_lists_work_bytes": [c_int64, c_int64],
+    "rvc_kmeans_lists": [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
+    "rvc_kmeans_update": [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    "rvc_gather_rows": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "rvc_crepe_frames": [c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p],
     "rvc_bn_maxpool": [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
                        c_void_p],
@@ -314,7 +321,8 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_fe0_ws_bytes": c_int64, "rvc_harmonic_source_ws_bytes": c_int64,
              "rvc_harmonic_source_chunk": c_int64, "rvc_swipe_frames": c_int64, "rvc_swipe_work_bytes": c_int64,
              "rvc_swipe_tables_bytes": c_int64, "rvc_swipe_table_dims": c_int64,
-             "rvc_abs_quantile_work_bytes": c_int64, "rvc_formant_work_bytes": c_int64}
+             "rvc_abs_quantile_work_bytes": c_int64, "rvc_formant_work_bytes": c_int64,
+             "rvc_kmeans_assign_work_bytes": c_int64, "rvc_kmeans_lists_work_bytes": c_int64}
 
 _lib = None
 

@@ -1054,6 +1054,73 @@ def ivf_blend(feats, nq, d, fcs, fqs, D, I, k, big, ntotal, index_rate, out, ocs
                                     _p(out), ocs, oqs, _stream()), "ivf_blend")
 
 
+def _rows(x, what):
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+        raise TypeError(f"{what}: a contiguous CUDA f32 [rows][d] tensor")
+    return x.shape
+
+
+def kmeans_assign(x, cent, assign=None, dist=None):
+    """Nearest centroid of every row of x [n][d] (kmeans.hip): (assign int32 [n], dist f32 [n])."""
+    (n, d), (k, dc) = _rows(x, "kmeans_assign"), _rows(cent, "kmeans_assign")
+    if dc != d:
+        raise ValueError(f"kmeans_assign: centroid dim {dc} != {d}")
+    assign = torch.empty(n, dtype=torch.int32, device=x.device) if assign is None else assign
+    dist = torch.empty(n, dtype=torch.float32, device=x.device) if dist is None else dist
+    if assign.numel() < n or dist.numel() < n or assign.dtype != torch.int32:
+        raise ValueError("kmeans_assign: output buffers too small")
+    lib = _lib.load()
+    need = lib.rvc_kmeans_assign_work_bytes(n, d, k)
+    if need < 0:
+        raise ValueError(f"kmeans_assign: bad sizes n={n} d={d} k={k}")
+    ws = _workspace(x.device, need, "kmeans")
+    check(lib.rvc_kmeans_assign(_p(x), n, d, _p(cent), k, _p(ws), need, _p(assign), _p(dist), _stream()),
+          "kmeans_assign")
+    return assign, dist
+
+
+def kmeans_lists(assign, k):
+    """Stable counting sort of the rows by list: (list_off int64 [k + 1], ids int64 [n], counts int32 [k])."""
+    if assign.dim() != 1 or assign.dtype != torch.int32 or not assign.is_contiguous():
+        raise TypeError("kmeans_lists: a contiguous CUDA int32 [n] tensor")
+    n = assign.numel()
+    lib = _lib.load()
+    need = lib.rvc_kmeans_lists_work_bytes(n, k)
+    if need < 0:
+        raise ValueError(f"kmeans_lists: bad sizes n={n} k={k}")
+    ws = _workspace(assign.device, need, "kmeans_lists")
+    list_off = torch.empty(k + 1, dtype=torch.int64, device=assign.device)
+    ids = torch.empty(n, dtype=torch.int64, device=assign.device)
+    counts = torch.empty(k, dtype=torch.int32, device=assign.device)
+    check(lib.rvc_kmeans_lists(_p(assign), n, k, _p(ws), need, _p(list_off), _p(ids), _p(counts), _stream()),
+          "kmeans_lists")
+    return list_off, ids, counts
+
+
+def kmeans_update(x, list_off, ids, cent_prev, out=None):
+    """faiss compute_centroids over the CSR lists: new centroids [k][d]; empty lists keep cent_prev's row."""
+    (n, d), (k, dc) = _rows(x, "kmeans_update"), _rows(cent_prev, "kmeans_update")
+    if dc != d or list_off.numel() < k + 1 or ids.numel() < n or list_off.dtype != torch.int64 or \
+            ids.dtype != torch.int64:
+        raise ValueError("kmeans_update: size mismatch")
+    out = torch.empty_like(cent_prev) if out is None else out
+    if out.shape != cent_prev.shape or out.data_ptr() == cent_prev.data_ptr():
+        raise ValueError("kmeans_update: out must be a separate [k][d] tensor")
+    check(_lib.load().rvc_kmeans_update(_p(x), n, d, _p(list_off), _p(ids), k, _p(cent_prev), _p(out), _stream()),
+          "kmeans_update")
+    return out
+
+
+def gather_rows(x, ids):
+    """out [m][d] = x[ids] for int64 device ids the caller knows to lie in [0, n)."""
+    n, d = _rows(x, "gather_rows")
+    if ids.dim() != 1 or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise TypeError("gather_rows: a contiguous CUDA int64 [m] tensor")
+    out = torch.empty(ids.numel(), d, dtype=torch.float32, device=x.device)
+    check(_lib.load().rvc_gather_rows(_p(x), d, _p(ids), ids.numel(), _p(out), _stream()), "gather_rows")
+    return out
+
+
 def phone_upsample(feats, feats0, pitchf, out, C, Tf, T, protect):
     if feats.numel() < C * Tf or out.numel() < C * T or T > 2 * Tf or (pitchf is not None and pitchf.numel() < T):
         raise ValueError("phone_upsample: size mismatch")

@@ -35,6 +35,21 @@ class IVFFlatDevice:
     def from_file(cls, path, device="cuda"):
         return cls(read_index(path), device)
 
+    @classmethod
+    def from_lists(cls, centroids, list_off, ids, codes, big, nprobe=1):
+        """A freshly built index (index_train.build_lists) straight from its device arrays, no file round trip:
+        centroids [nlist][d], CSR list_off int64 [nlist + 1], ids int64 [n] and list-major codes [n][d], and
+        big [n][d] = the rows in id order (what reconstruct_n(0, n) returns)."""
+        self = cls.__new__(cls)
+        self.nlist, self.d = (int(v) for v in centroids.shape)
+        self.nprobe, self.ntotal, self.device = int(nprobe), int(ids.numel()), centroids.device
+        if list_off.numel() != self.nlist + 1 or tuple(codes.shape) != (self.ntotal, self.d) or \
+                tuple(big.shape) != (self.ntotal, self.d):
+            raise ValueError("IVFFlatDevice.from_lists: array shapes do not describe one index")
+        self.centT = centroids.t().contiguous()
+        self.list_off, self.ids, self.codes, self.big = list_off, ids, codes.contiguous(), big.contiguous()
+        return self
+
     def search_cf(self, feats_cf, k=8, nprobe=None, arithmetic="faiss"):
         """feats_cf [d][T] device f32 (channels-first) -> (D [T][k] f32, I [T][k] int64).  ``arithmetic``:
         "faiss" = faiss's own f32 evaluation (the default; include/rvc_amd.h), "exact" = f64 (diagnostic)."""

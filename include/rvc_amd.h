@@ -566,6 +566,49 @@ int rvc_abs_quantile(const float* x, int64_t n, void* work, int64_t work_bytes, 
 int rvc_div_scalar(const float* x, int64_t n, const float* q, float* out, rvc_stream_t stream);
 int rvc_f0_mix(const rvc_f0_track* tracks, int M, int64_t p_len, double* out, rvc_stream_t stream);
 
+/* fcpe f0 (VC.get_f0_fcpe, convert.py:239-246: the conv-only CFNaiveMelPE of main/library/predictors/FCPE.py).
+ * A host runs, per signal: rvc_fcpe_mel; rvc_conv1d (k=3, 128 -> C); rvc_groupnorm_act; rvc_conv1d (k=3);
+ * per layer rvc_layernorm_cf, rvc_conv1d (1x1, C -> 4C), rvc_glu_dwconv_silu, rvc_conv1d (1x1, 2C -> C, res =
+ * the layer's input); rvc_layernorm_cf; rvc_conv1d (1x1, C -> 360, out_act = sigmoid); rvc_fcpe_decode;
+ * rvc_fcpe_post; rvc_pm_post (nf = p_len).  All tensors channels-first [B][C][T] f32.
+ *   rvc_fcpe_mel         MelModule.__call__ at key_shift 0, speed 1 + Wav2MelModule's frame fix-up
+ *                        (FCPE.py:838-876, 898-913): x [B][N] at 16 kHz, reflect-padded by 432 on both sides,
+ *                        non-centred frames of 1024 at hop 160 under a periodic Hann window, sqrt(re^2 + im^2 +
+ *                        1e-9), basis [128][513] (f32), log(max(., 1e-5)) -> mel [B][128][T], T = N / 160 + 1,
+ *                        frame T-1 a copy of frame T-2.  f64 FFT and sums, rounded to f32 once.  N <= 432 (where
+ *                        the reference switches to constant padding) is rejected with RVC_EINVAL.
+ *   rvc_groupnorm_act    GroupNorm(G, C) over (C/G) x T per batch element (f64 statistics, biased variance),
+ *                        affine, then LeakyReLU(slope) (FCPE.py:422; slope 1 = none); work:
+ *                        rvc_groupnorm_work_bytes(B, G) bytes
+ *   rvc_glu_dwconv_silu  ConformerConvModule's middle (FCPE.py:550): x [B][2H][T] -> u = x[:H] * sigmoid(x[H:]),
+ *                        depthwise conv of K taps (K odd <= 31, zero padding K/2, w [H][K], bias [H]), SiLU ->
+ *                        y [B][H][T].  One block per channel and RVC_GLU_DW_TILE time steps.
+ *   rvc_fcpe_decode      latent2cents_local_decoder + cent_to_f0 + infer's masks (FCPE.py:451-468, 479-480,
+ *                        751-756) on the LATENT (after the sigmoid) [B][C][T], C >= 1: first-index argmax, the 9
+ *                        bins argmax-4..argmax+4 clamped into [0, C-1] (a clamped bin counts again),
+ *                        sum(cent_table * y) / sum(y) and 10 * 2^(cents / 1200) in f32; confidence <= threshold
+ *                        -> 0, f0 < f0_min -> 0, f0 > f0_max -> f0_max  -> f0 f32 [B][T]
+ *   rvc_fcpe_post        the rest of infer, then FCPE.compute_f0 / post_process (FCPE.py:757-759, 975-1000) on one
+ *                        track f0 f32 [T]: zeros -> NaN, F.interpolate(mode="linear") to p_len as torch's CPU
+ *                        kernel evaluates it in f32 (a copy when p_len == T), NaN -> 0; no voiced frame -> zeros,
+ *                        one -> p_len copies of it, else np.interp in f64 over the voiced frames (nodes
+ *                        (hop_length / sample_rate) * idx, queries i * hop_length / sample_rate, ends held)
+ *                        -> out f64 [p_len].  One block, no host read-back; work: rvc_fcpe_post_work_bytes(p_len)
+ * No entry synchronises or allocates. */
+enum { RVC_GLU_DW_TILE = 256, RVC_FCPE_MELS = 128, RVC_FCPE_NFFT = 1024, RVC_FCPE_HOP = 160 };
+int rvc_fcpe_mel(const float* x, const float* basis, float* mel, int64_t B, int64_t N, rvc_stream_t stream);
+int64_t rvc_groupnorm_work_bytes(int64_t B, int G);
+int rvc_groupnorm_act(const float* x, const float* gamma, const float* beta, float* y, int64_t B, int64_t C,
+                      int64_t T, int G, float eps, float slope, void* work, int64_t work_bytes,
+                      rvc_stream_t stream);
+int rvc_glu_dwconv_silu(const float* x, const float* w, const float* bias, float* y, int64_t B, int64_t H,
+                        int64_t T, int K, rvc_stream_t stream);
+int rvc_fcpe_decode(const float* latent, const float* cent_table, float* f0, int64_t B, int64_t C, int64_t T,
+                    float threshold, float f0_min, float f0_max, rvc_stream_t stream);
+int64_t rvc_fcpe_post_work_bytes(int64_t p_len); /* -1 for p_len <= 0 or p_len >= 2^24 */
+int rvc_fcpe_post(const float* f0, int64_t T, int64_t p_len, int hop_length, int sample_rate, void* work,
+                  int64_t work_bytes, double* out, rvc_stream_t stream);
+
 /* ------------------------------------------------------------------ VC.pipeline glue
  * phone_upsample: nearest x2 + protect blend (convert.py:361-378) -> phone [C][T]
  * peak_normalize: x /= max|x|/0.99 when > 1 (convert.py:450-451); ws: 16 B scratch;

@@ -173,6 +173,14 @@ SIGNATURES = {
     "rvc_abs_quantile": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "rvc_div_scalar": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     "rvc_f0_mix": [POINTER(F0Track), c_int, c_int64, c_void_p, c_void_p],
+    "rvc_fcpe_mel": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
+    "rvc_groupnorm_work_bytes": [c_int64, c_int],
+    "rvc_groupnorm_act": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_float, c_float,
+                          c_void_p, c_int64, c_void_p],
+    "rvc_glu_dwconv_silu": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p],
+    "rvc_fcpe_decode": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float, c_float, c_void_p],
+    "rvc_fcpe_post_work_bytes": [c_int64],
+    "rvc_fcpe_post": [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p],
     "rvc_conv1d_pack_f16": [c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, POINTER(c_int), c_void_p],
     "rvc_attention_workspace_bytes": [POINTER(AttnArgs)],
     "rvc_attention": [POINTER(AttnArgs), c_void_p, c_int64, c_void_p],
@@ -322,7 +330,8 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_harmonic_source_chunk": c_int64, "rvc_swipe_frames": c_int64, "rvc_swipe_work_bytes": c_int64,
              "rvc_swipe_tables_bytes": c_int64, "rvc_swipe_table_dims": c_int64,
              "rvc_abs_quantile_work_bytes": c_int64, "rvc_formant_work_bytes": c_int64,
-             "rvc_kmeans_assign_work_bytes": c_int64, "rvc_kmeans_lists_work_bytes": c_int64}
+             "rvc_kmeans_assign_work_bytes": c_int64, "rvc_kmeans_lists_work_bytes": c_int64,
+             "rvc_groupnorm_work_bytes": c_int64, "rvc_fcpe_post_work_bytes": c_int64}
 
 _lib = None
 

@@ -19,15 +19,17 @@ def is_hybrid(f0_method: str) -> bool:
     return "hybrid" in f0_method  # the reference's own test (convert.py:306)
 
 
-def parse_hybrid(f0_method: str) -> list[str]:
+def parse_hybrid(f0_method: str, extra=()) -> list[str]:
     """"hybrid[a+b]" -> ["a", "b"] as get_f0_hybrid parses it; a member that is not on the device path raises
-    NotImplementedError naming it.  A repeated member stays repeated (the reference computes it again)."""
+    NotImplementedError naming it.  A repeated member stays repeated (the reference computes it again).
+    ``extra`` names members the caller accepts beyond MEMBERS (VC and FeatureInputAMD pass ("fcpe",): they hold
+    the model it needs)."""
     m = re.search(r"hybrid\[(.+)\]", f0_method)
     if not m:
         raise ValueError(f"f0 method {f0_method!r}: expected hybrid[a+b+...]")
     members = [s.strip() for s in m.group(1).split("+")]
     for name in members:
-        if name not in MEMBERS:
+        if name not in MEMBERS and name not in extra:
             raise NotImplementedError(f"hybrid f0 member {name!r}: rmvpe, crepe-*, pm and swipe are on the "
                                       "MI355X path")
     if len(members) > MAX_TRACKS:

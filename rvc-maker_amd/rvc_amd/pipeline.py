@@ -92,8 +92,9 @@ class Config:
 
 class VC:
     CREPE_METHODS = {f"crepe-{c}": c for c in ("tiny", "small", "medium", "large", "full")}
+    HYBRID_EXTRA = ("fcpe",)  # hybrid members beyond f0mix.MEMBERS: the ones that need a model VC holds
 
-    def __init__(self, tgt_sr, config, rmvpe=None, crepe=None):
+    def __init__(self, tgt_sr, config, rmvpe=None, crepe=None, fcpe=None):
         self.x_pad = config.x_pad
         self.x_query = config.x_query
         self.x_center = config.x_center
@@ -110,6 +111,7 @@ class VC:
         self.device = config.device
         self.is_half = config.is_half
         self.rmvpe = rmvpe
+        self.fcpe = fcpe  # FcpeAMD (loaded on first use otherwise)
         # library-created streams (CU-masked) this VC owns: destroyed by close() / at exit, after their work
         self._owned = []
         self._finalizer = weakref.finalize(self, _close_streams, self._owned)
@@ -143,6 +145,12 @@ class VC:
             self.rmvpe = RMVPEAMD.from_file(os.path.join("assets", "models", "predictors", "rmvpe.pt"), self.device)
         return self.rmvpe
 
+    def _fcpe(self):
+        if self.fcpe is None:
+            from .fcpe import FcpeAMD
+            self.fcpe = FcpeAMD.from_file(os.path.join("assets", "models", "predictors", "fcpe.pt"), self.device)
+        return self.fcpe
+
     def _crepe(self, capacity):
         if capacity not in self.crepe:
             from .crepe import CrepeAMD
@@ -151,10 +159,11 @@ class VC:
         return self.crepe[capacity]
 
     def f0_device(self, xp, pitch, f0_method="rmvpe", f0_autotune=False, f0_autotune_strength=1.0, inp_f0=None,
-                  xp64=None):
+                  xp64=None, hop_length=64):
         """VC.get_f0 (convert.py:304-323) on the device: (coarse int64 [T], pitchf f32 [T]).  Autotune
         and the f0-file override run inside the decode kernels, in the reference's order.  "pm" reads the
-        f64 signal ``xp64`` (the reference hands parselmouth the f64 filtfilt output)."""
+        f64 signal ``xp64`` (the reference hands parselmouth the f64 filtfilt output); ``hop_length`` is the one
+        ``pipeline`` receives, which only "fcpe" (alone or as a hybrid member) reads."""
         post = None
         if f0_autotune or inp_f0 is not None:
             rep, off = f0_override(inp_f0, self.x_pad) if inp_f0 is not None else (None, 0)
@@ -175,10 +184,16 @@ class VC:
             # get_f0_swipe reads x.astype(np.float32) of the f64 filtered signal: xp is that rounding already
             # (filtfilt.hip's filt_reflect_pad stores (float)v beside the f64 v)
             return self._swipe(xp.device).f0_device(xp.contiguous(), float(pitch), post=post)
+        if f0_method == "fcpe":
+            # get_f0_fcpe (convert.py:239-246): the reference truncates f0_min / f0_max and the hop length
+            return self._fcpe().f0_device(xp.contiguous(), float(pitch), xp.numel() // self.window, post=post,
+                                          hop_length=int(hop_length), f0_min=int(self.f0_min),
+                                          f0_max=int(self.f0_max))
         if f0mix.is_hybrid(f0_method):
-            return self._f0_hybrid(xp, float(pitch), f0mix.parse_hybrid(f0_method), post)
-        raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe and hybrid[...] over them "
-                                  "are on the MI355X path")
+            return self._f0_hybrid(xp, float(pitch), f0mix.parse_hybrid(f0_method, extra=self.HYBRID_EXTRA), post,
+                                   hop_length)
+        raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe, fcpe and hybrid[...] over "
+                                  "them are on the MI355X path")
 
     def _swipe(self, device):
         if getattr(self, "swipe", None) is None:
@@ -186,10 +201,10 @@ class VC:
             self.swipe = SwipeAMD(device)
         return self.swipe
 
-    def f0_raw(self, x32, member, p_len):
+    def f0_raw(self, x32, member, p_len, hop_length=64):
         """One estimator's raw track (before any shift / autotune) on the device f32 signal x32, as
         get_f0_hybrid's members return it: rmvpe f64 [1 + N//160], crepe-* f32 [1 + N//160], pm f64 padded to
-        p_len, swipe f32 [1 + N//160]."""
+        p_len, swipe f32 [1 + N//160], fcpe f64 [p_len]."""
         if member == "rmvpe":
             return self._rmvpe().f0_device(x32, 0.03, 0.0, want_f0=True)[2]
         if member in self.CREPE_METHODS:
@@ -206,15 +221,18 @@ class VC:
             return f0
         if member == "swipe":
             return self._swipe(x32.device).f0(x32)
-        raise NotImplementedError(f"hybrid f0 member {member!r}: rmvpe, crepe-*, pm and swipe are on the MI355X path")
+        if member == "fcpe":
+            return self._fcpe().f0(x32, p_len, int(hop_length), 0.006, int(self.f0_min), int(self.f0_max))
+        raise NotImplementedError(f"hybrid f0 member {member!r}: rmvpe, crepe-*, pm, swipe and fcpe are on the "
+                                  "MI355X path")
 
-    def _f0_hybrid(self, xp, pitch, members, post):
+    def _f0_hybrid(self, xp, pitch, members, post, hop_length=64):
         """get_f0_hybrid + get_f0's post (convert.py:283-323): every member reads the f32 signal divided by its
         0.999 |x| quantile; the raw tracks are resampled to p_len and their nanmedian taken, in f64."""
         from . import pm as _pm
         p_len = xp.numel() // self.window
         xn = f0mix.normalize(xp.contiguous())
-        f0 = f0mix.mix([self.f0_raw(xn, m, p_len) for m in members], p_len)
+        f0 = f0mix.mix([self.f0_raw(xn, m, p_len, hop_length) for m in members], p_len)
         coarse = torch.empty(p_len, dtype=torch.int64, device=xp.device)
         pitchf = torch.empty(p_len, device=xp.device)
         ops.check(_lib.load().rvc_pm_post(_pm._p64(f0), p_len, p_len, float(2.0 ** (pitch / 12)),
@@ -325,7 +343,7 @@ class VC:
 
     def pipeline_device(self, model, net_g, sid, audio, pitch, version, protect, index=None, index_rate=0.0,
                         f0_method="rmvpe", f0_autotune=False, f0_autotune_strength=1.0, inp_f0=None,
-                        volume_envelope=1.0):
+                        volume_envelope=1.0, hop_length=64):
         """The hot path with inputs and output in HBM: audio device f32 [N] at 16 kHz (numpy accepted)
         -> device f32 waveform at tgt_sr.  filtfilt + reflect padding run on the device (f64)."""
         if not torch.is_tensor(audio):
@@ -339,7 +357,8 @@ class VC:
             opt_ts = ops.quiet_points(xp64[self.t_pad: self.t_pad + N], self.window, self.t_center, self.t_query,
                                       self.t_max)
         p_len = xp.numel() // self.window
-        f0_opts = dict(f0_autotune=f0_autotune, f0_autotune_strength=f0_autotune_strength, inp_f0=inp_f0)
+        f0_opts = dict(f0_autotune=f0_autotune, f0_autotune_strength=f0_autotune_strength, inp_f0=inp_f0,
+                       hop_length=hop_length)
         src64 = xp64[self.t_pad: self.t_pad + N] if volume_envelope != 1 else None
         return self._pipeline_on_device(model, net_g, sid, xp, opt_ts, p_len, pitch, version, protect, index,
                                         index_rate, f0_method, f0_opts, volume_envelope, src64, xp64)
@@ -715,10 +734,11 @@ class VC:
         if f0_onnx:
             raise NotImplementedError("f0_onnx: ONNX f0 models are not on the MI355X path")
         if f0mix.is_hybrid(f0_method):
-            f0mix.parse_hybrid(f0_method)  # raises, naming the member, for one that is not on the device path
-        elif f0_method not in ("rmvpe", "pm", "swipe") and f0_method not in self.CREPE_METHODS:
-            raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe and hybrid[...] over "
-                                      "them are on the MI355X path")
+            # raises, naming the member, for one that is not on the device path
+            f0mix.parse_hybrid(f0_method, extra=self.HYBRID_EXTRA)
+        elif f0_method not in ("rmvpe", "pm", "swipe", "fcpe") and f0_method not in self.CREPE_METHODS:
+            raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe, fcpe and hybrid[...] "
+                                      "over them are on the MI355X path")
         index = None
         if file_index != "" and os.path.exists(file_index) and index_rate != 0:  # convert.py:392-399
             index = self._index(file_index)
@@ -737,7 +757,7 @@ class VC:
         try:
             out = self.pipeline_device(model, net_g, int(sid), np.asarray(audio, dtype=np.float32), pitch, version,
                                        protect, index, index_rate, f0_method, bool(f0_autotune), f0_autotune_strength,
-                                       inp_f0, volume_envelope)
+                                       inp_f0, volume_envelope, hop_length=int(hop_length))
         finally:
             self.embed_suffix = prev
         if pbar is not None:

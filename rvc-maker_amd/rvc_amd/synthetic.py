@@ -419,6 +419,56 @@ def crepe_state_dict(seed: int = 999, capacity: str = "full") -> "OrderedDict[st
     return sd
 
 
+FCPE_MEL = {"type": "default", "sr": 16000, "num_mels": 128, "n_fft": 1024, "win_size": 1024, "hop_size": 160,
+            "fmin": 0, "fmax": 8000}
+# gains of the synthetic FCPE: default-scale weights decode every frame to one bin, so the body convs are scaled
+# up until the argmax moves with the input, and the output bias puts the confidence threshold (0.006) inside
+# the range the top latent covers (tests/golden/make_golden_fcpe.py asserts what the fixture needs)
+FCPE_BODY_GAIN, FCPE_OUT_GAIN, FCPE_OUT_BIAS = 1.0, 3.0, -14.6
+
+
+def fcpe_checkpoint(seed: int = 2028, n_layers: int = 6, hidden_dims: int = 512,
+                    use_harmonic_emb: bool = False) -> dict:
+    """A seeded ``fcpe.pt`` in the reference's layout (FCPE.py:807-810): {"config_dict": {"mel", "model"},
+    "model": CFNaiveMelPE.state_dict()} of a conv-only model (tests/golden/fcpe_keys.json lists the keys)."""
+    g = _Gen(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    C, f0_min, f0_max = hidden_dims, 32.70, 1975.5
+    cents = [1200 * torch.log2(torch.Tensor([f]) / 10)[0] for f in (f0_min, f0_max)]
+    sd["cent_table"] = torch.linspace(cents[0], cents[1], 360)
+    sd["gaussian_blurred_cent_mask"] = (1200 * torch.log2(torch.Tensor([f0_max / 10.])))[0]
+    if use_harmonic_emb:
+        sd["harmonic_emb.weight"] = g.normal((9, C), 0.1)
+
+    def norm(name):
+        sd[name + ".weight"] = g.uniform((C,), 0.7, 1.3)
+        sd[name + ".bias"] = g.normal((C,), 0.1)
+
+    # the log-mel input is mostly a constant floor (log 1e-5 in the empty bands): taps that sum to zero pass on
+    # only what changes from frame to frame, or the constant part would decide every frame's argmax alike
+    _conv(g, sd, "input_stack.0", C, 128, 3)
+    sd["input_stack.0.weight"] -= sd["input_stack.0.weight"].mean(dim=2, keepdim=True)
+    norm("input_stack.1")
+    _conv(g, sd, "input_stack.3", C, C, 3, gain=FCPE_BODY_GAIN)
+    for i in range(n_layers):
+        p = f"net.encoder_layers.{i}."
+        norm(p + "conformer.net.0")
+        _conv(g, sd, p + "conformer.net.2", 4 * C, C, 1, gain=FCPE_BODY_GAIN)
+        _conv(g, sd, p + "conformer.net.4.conv", 2 * C, 1, 31, gain=FCPE_BODY_GAIN)
+        _conv(g, sd, p + "conformer.net.6", C, 2 * C, 1, gain=FCPE_BODY_GAIN)
+        norm(p + "norm")  # the attention branch's LayerNorm: unused when conv_only
+    norm("norm")
+    sd["output_proj.bias"] = g.normal((360,), 0.5) + FCPE_OUT_BIAS
+    v = g.normal((360, C), 1.0 / math.sqrt(C))
+    sd["output_proj.parametrizations.weight.original0"] = \
+        v.pow(2).sum(dim=1, keepdim=True).sqrt() * g.uniform((360, 1), 0.7, 1.3) * FCPE_OUT_GAIN
+    sd["output_proj.parametrizations.weight.original1"] = v
+    model = {"type": "CFNaiveMelPE", "out_dims": 360, "hidden_dims": C, "n_layers": n_layers, "n_heads": 8,
+             "f0_min": f0_min, "f0_max": f0_max, "use_fa_norm": False, "conv_only": True, "conv_dropout": 0.1,
+             "atten_dropout": 0.1, "use_harmonic_emb": bool(use_harmonic_emb)}
+    return {"config_dict": {"mel": dict(FCPE_MEL), "model": model}, "model": sd}
+
+
 # ---------------------------------------------------------------- audio
 def synthetic_audio(seconds: float, seed: int = 1000, sr: int = 16000) -> np.ndarray:
     """SURVEY §8(d) test signal: 3-harmonic glide (60-240 Hz) + 200 ms gaps every 5 s + noise, peak <= 0.9."""

@@ -935,6 +935,48 @@ int rvc_vc_convert_ex(rvc_ctx* ctx, const float* audio, int64_t N, const rvc_vc_
 int rvc_crepe_f0(rvc_ctx* ctx, const float* audio, int64_t N, const float* dither, uint64_t seed, double pitch_shift,
                  const rvc_f0_post* post, float* probs, int64_t* coarse, float* pitchf, rvc_stream_t stream);
 
+/* ------------------------------------------------------------------ dataset preprocessing
+ * PreProcess.process_audio (main/inference/preprocess.py:129-185) in f64 (preprocess.hip).  No entry synchronises
+ * or allocates; x_is_f64 selects f64 (!= 0) or f32 input samples; every pointer is device memory unless it says HOST.
+ *
+ * lfilter64: scipy.signal.lfilter(b, a, x) for order 5 from a zero state (preprocess.py:160): x [N] -> y f64 [N].
+ *   b[6], a[6] are HOST arrays (normalised by a[0] as scipy does).  The signal is cut into RVC_LFILTER_CHUNK-sample
+ *   chunks, one per lane (RVC_LFILTER_WAVE samples per 64-lane block); a lane rebuilds its entry state by running
+ *   the recurrence over the `warm` samples before its chunk, staged in tiles of RVC_LFILTER_TILE samples.
+ *   warm = rvc_lfilter64_warmup(b, a): the first multiple of the tile past the last sample whose |impulse response|
+ *   is >= 1e-12, or -1 for a filter that needs more than RVC_LFILTER_WARM_CAP (rvc_lfilter64 rejects those).
+ *   work: rvc_lfilter64_work_bytes(N, warm) bytes of scratch (0 today, NULL is accepted then; -1 on bad arguments).
+ * frame_rms64: get_rms (preprocess.py:119-127): constant padding of frame / 2 each side, frames of `frame` samples
+ *   every `hop`, sqrt(mean(x^2)) summed in f64 in a fixed order -> out f64 [rvc_frame_rms64_len(N, frame, hop)]
+ *   (= 1 + N / hop for an even frame).
+ * peak_mix64: _normalize_audio (preprocess.py:142-145): *peak = max|x| (exact; a NaN sample gives NaN), then
+ *   y = (x / *peak * gain) + rest * x with numpy's roundings (y may be x).  The caller reads *peak back and takes the
+ *   reference's `> 2.5` decision.
+ * resample_poly64: scipy.signal.resample_poly(x, up, down) (padtype "constant") of nseg chunks in one launch.
+ *   h f64 [h_len]: firwin(2 * 10 * max(up, down) + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up behind
+ *   scipy's n_pre_pad zeros; n_pre_remove as scipy computes it.  seg int64 [nseg][4] = (in_offset, in_len, out_offset,
+ *   out_len), out_len = ceil(in_len * up / down), given twice with the same contents: seg_host (HOST, validated
+ *   against n_in / n_out before the launch) and seg_dev (device, read by the kernel).  Every chunk sees zeros outside
+ *   its own samples.  y64 f64 [n_out] and y32 = the same values cast to f32. */
+enum {
+    RVC_LFILTER_CHUNK = 512,        /* output samples per lane */
+    RVC_LFILTER_WAVE = 64 * 512,    /* output samples per block (one wave) */
+    RVC_LFILTER_TILE = 32,          /* samples per staged tile; warm is a multiple of it */
+    RVC_LFILTER_WARM_CAP = 16384    /* longest supported warm-up */
+};
+int64_t rvc_lfilter64_warmup(const double* b, const double* a);
+int64_t rvc_lfilter64_work_bytes(int64_t N, int64_t warm);
+int rvc_lfilter64(const void* x, int x_is_f64, int64_t N, const double* b, const double* a, int64_t warm, void* work,
+                  int64_t work_bytes, double* y, rvc_stream_t stream);
+int64_t rvc_frame_rms64_len(int64_t N, int64_t frame, int64_t hop);
+int rvc_frame_rms64(const void* x, int x_is_f64, int64_t N, int64_t frame, int64_t hop, double* out,
+                    rvc_stream_t stream);
+int rvc_peak_mix64(const double* x, int64_t N, double gain, double rest, double* peak, double* y,
+                   rvc_stream_t stream);
+int rvc_resample_poly64(const void* x, int x_is_f64, int64_t n_in, const double* h, int64_t h_len, int up, int down,
+                        int64_t n_pre_remove, const int64_t* seg_host, const int64_t* seg_dev, int64_t nseg,
+                        double* y64, float* y32, int64_t n_out, rvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("RVC_AMD_LIB") or os.path.join(
     os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "librvc_amd.so")
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH, ACT_GELU, ACT_SIGMOID, ACT_LOGCLAMP = 0, 1, 2, 3, 4, 5, 6
+# rvc_lfilter64's geometry (the RVC_LFILTER_* enum of the header)
+LFILTER_CHUNK, LFILTER_WAVE, LFILTER_TILE, LFILTER_WARM_CAP = 512, 64 * 512, 32, 16384
 
 
 class Conv1dArgs(ctypes.Structure):
@@ -315,6 +317,14 @@ SIGNATURES = {
                      c_void_p, c_void_p],
     "rvc_synth_infer": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_uint64,
                         c_void_p, c_void_p],
+    "rvc_lfilter64_warmup": [c_void_p, c_void_p],
+    "rvc_lfilter64_work_bytes": [c_int64, c_int64],
+    "rvc_lfilter64": [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
+    "rvc_frame_rms64_len": [c_int64, c_int64, c_int64],
+    "rvc_frame_rms64": [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p],
+    "rvc_peak_mix64": [c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p],
+    "rvc_resample_poly64": [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p,
+                            c_int64, c_void_p, c_void_p, c_int64, c_void_p],
 }
 _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_int64, "rvc_conv1d_x6_bytes": c_int64,
              "rvc_conv64_workspace_bytes": c_int64, "rvc_wino64_workspace_bytes": c_int64,
@@ -331,7 +341,8 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_swipe_tables_bytes": c_int64, "rvc_swipe_table_dims": c_int64,
              "rvc_abs_quantile_work_bytes": c_int64, "rvc_formant_work_bytes": c_int64,
              "rvc_kmeans_assign_work_bytes": c_int64, "rvc_kmeans_lists_work_bytes": c_int64,
-             "rvc_groupnorm_work_bytes": c_int64, "rvc_fcpe_post_work_bytes": c_int64}
+             "rvc_groupnorm_work_bytes": c_int64, "rvc_fcpe_post_work_bytes": c_int64,
+             "rvc_lfilter64_warmup": c_int64, "rvc_lfilter64_work_bytes": c_int64, "rvc_frame_rms64_len": c_int64}
 
 _lib = None
 

@@ -68,3 +68,9 @@ def write_wav(path: str, audio: np.ndarray, sr: int) -> None:
     """sf.write(path, audio, sr, format="wav"): PCM_16 (clipped to [-1, 1], scaled by 32767)."""
     pcm = np.round(np.clip(np.asarray(audio, np.float64), -1.0, 1.0) * 32767.0).astype(np.int16)
     wavfile.write(path, int(sr), pcm)
+
+
+def write_wav_f32(path: str, audio: np.ndarray, sr: int) -> None:
+    """wavfile.write(path, sr, audio.astype(np.float32)): an IEEE-float WAV, as dataset preprocessing writes its
+    slices (main/inference/preprocess.py:152-153)."""
+    wavfile.write(path, int(sr), np.asarray(audio).astype(np.float32))

@@ -609,6 +609,30 @@ int64_t rvc_fcpe_post_work_bytes(int64_t p_len); /* -1 for p_len <= 0 or p_len >
 int rvc_fcpe_post(const float* f0, int64_t T, int64_t p_len, int hop_length, int sample_rate, void* work,
                   int64_t work_bytes, double* out, rvc_stream_t stream);
 
+/* fcpe-legacy f0 (get_f0_fcpe(legacy=True): FCPE_LEGACY behind Wav2Mel, threshold 0.03).  The front end, the stack,
+ * the Conformer conv module, the decoder and the post stages are the entries above (rvc_fcpe_decode with f0_min = 0
+ * and f0_max = FLT_MAX: the legacy model has no range clamp); a layer adds, before its conv module, rvc_layernorm_cf;
+ * rvc_conv1d (1x1, C -> 3 * 512: to_q, to_k, to_v stacked); rvc_performer_attention; rvc_conv1d (1x1, 512 -> C,
+ * res = the layer's input).
+ *   rvc_performer_attention  FAVOR+ linear attention (FCPE.py:87-88, 108-116, 576-583), non-causal, no mask, per
+ *                        batch element and head, D = 64 channels per head, proj [M][64] (16-byte aligned),
+ *                        1 <= M <= RVC_PERFORMER_MAX_FEATURES, c = 64^-0.25, r = M^-0.5:
+ *                          dq[t][j] = c q[t].proj[j]   gq[t] = 0.5 c^2 |q[t]|^2   (dk, gk likewise)
+ *                          q'[t][j] = r (exp(dq - gq - max_j dq) + 1e-4)    k'[t][j] = r exp(dk - gk + 1e-4)
+ *                          out[t] = (q'[t] . sum_t k'[t]^T v[t]) / (q'[t] . sum_t k'[t] + 1e-8)
+ *                        q, k, v, out channels-first: head h is channels 64 h .. 64 h + 63, channel stride ldc
+ *                        (0 = T), batch strides in_bs (q, k, v) and out_bs (0 = H * 64 * ldc), so q, k and v may be
+ *                        slices of one [B][3 * 64 H][T] buffer.  Every product is an f32 fma chain (f32-input MFMA);
+ *                        the partial sums over time are added in a fixed order, so two calls give the same bits.
+ *                        Anything else (D != 64, M out of range, a short work buffer) is RVC_EINVAL, before any
+ *                        launch.  work: rvc_performer_work_bytes(B, H, T, M) bytes (-1 for a bad shape), 16-byte
+ *                        aligned.  Time tiles are RVC_PERFORMER_TILE steps in both passes. */
+enum { RVC_PERFORMER_TILE = 32, RVC_PERFORMER_MAX_FEATURES = 272 };
+int64_t rvc_performer_work_bytes(int64_t B, int64_t H, int64_t T, int M);
+int rvc_performer_attention(const float* q, const float* k, const float* v, const float* proj, float* out, int64_t B,
+                            int64_t H, int64_t T, int D, int M, int64_t ldc, int64_t in_bs, int64_t out_bs, void* work,
+                            int64_t work_bytes, rvc_stream_t stream);
+
 /* ------------------------------------------------------------------ VC.pipeline glue
  * phone_upsample: nearest x2 + protect blend (convert.py:361-378) -> phone [C][T]
  * peak_normalize: x /= max|x|/0.99 when > 1 (convert.py:450-451); ws: 16 B scratch;

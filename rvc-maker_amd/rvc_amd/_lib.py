@@ -183,6 +183,9 @@ SIGNATURES = {
     "rvc_fcpe_decode": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float, c_float, c_void_p],
     "rvc_fcpe_post_work_bytes": [c_int64],
     "rvc_fcpe_post": [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p],
+    "rvc_performer_work_bytes": [c_int64, c_int64, c_int64, c_int],
+    "rvc_performer_attention": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
+                                c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p],
     "rvc_conv1d_pack_f16": [c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, POINTER(c_int), c_void_p],
     "rvc_attention_workspace_bytes": [POINTER(AttnArgs)],
     "rvc_attention": [POINTER(AttnArgs), c_void_p, c_int64, c_void_p],
@@ -342,6 +345,7 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_abs_quantile_work_bytes": c_int64, "rvc_formant_work_bytes": c_int64,
              "rvc_kmeans_assign_work_bytes": c_int64, "rvc_kmeans_lists_work_bytes": c_int64,
              "rvc_groupnorm_work_bytes": c_int64, "rvc_fcpe_post_work_bytes": c_int64,
+             "rvc_performer_work_bytes": c_int64,
              "rvc_lfilter64_warmup": c_int64, "rvc_lfilter64_work_bytes": c_int64, "rvc_frame_rms64_len": c_int64}
 
 _lib = None

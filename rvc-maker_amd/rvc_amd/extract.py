@@ -14,9 +14,10 @@ files are the only output, so there is no data-path collective, only a barrier b
 the file list.  Host-side steps (coarse quantiser, file naming, list building) follow the reference
 expression for expression; ``tests/golden/edges.npz`` pins ``coarse_f0`` against it.
 
-f0 methods on the device: ``rmvpe``, ``crepe-{tiny,...,full}``, ``swipe``, ``fcpe`` and ``hybrid[a+b+...]``
-over those and ``pm`` (the reference's other estimators -- harvest, dio, yin, pyin, fcpe-legacy, ... -- are
-third-party or off the path and raise).  Embedders: fairseq
+f0 methods on the device: ``rmvpe``, ``crepe-{tiny,...,full}``, ``swipe``, ``fcpe``, ``fcpe-legacy`` (when its
+model is given or ``assets/models/predictors/fcpe_legacy.pt`` exists) and ``hybrid[a+b+...]`` over those and ``pm``
+(the reference's other estimators -- harvest, dio, yin, pyin, ... -- are third-party or off the path and
+raise).  Embedders: fairseq
 ContentVec (``embedders_mode="fairseq"``).
 """
 from __future__ import annotations
@@ -37,7 +38,10 @@ log = logging.getLogger(__name__)
 class FeatureInputAMD:
     """extract.py:120-243 with the f0 estimators on the device."""
 
-    def __init__(self, sample_rate=16000, hop_size=160, device="cuda:0", rmvpe=None, crepe=None, fcpe=None):
+    FCPE_LEGACY_PT = os.path.join("assets", "models", "predictors", "fcpe_legacy.pt")
+
+    def __init__(self, sample_rate=16000, hop_size=160, device="cuda:0", rmvpe=None, crepe=None, fcpe=None,
+                 fcpe_legacy=None):
         self.fs = sample_rate
         self.hop = hop_size
         self.f0_bin = 256
@@ -49,11 +53,13 @@ class FeatureInputAMD:
         self.rmvpe = rmvpe
         self.crepe = dict(crepe or {})
         self.fcpe = fcpe
+        self.fcpe_legacy = fcpe_legacy
 
     def compute_f0(self, np_arr, f0_method, hop_length=160, f0_onnx=False):
         """extract.py:149-151 for the device methods: rmvpe -> f64 [1 + N//160] (RMVPE.infer_from_audio,
         thred 0.03); crepe-<cap> -> f32 [1 + N//160] (get_crepe, :173-180); fcpe -> f64 [N // 160] (get_fcpe,
-        :182-188, the only method that reads ``hop_length``)."""
+        :182-188; fcpe-legacy the same with legacy=True, threshold 0.03: the two methods that read
+        ``hop_length``)."""
         if f0_onnx:
             raise NotImplementedError(f"f0 method {f0_method!r} (onnx) is not on the device path")
         if "hybrid" in f0_method:
@@ -62,6 +68,8 @@ class FeatureInputAMD:
             return self._swipe().f0(self._dev32(np_arr)).cpu().numpy()
         if f0_method == "fcpe":
             return self._fcpe_f0(np_arr, hop_length).cpu().numpy()
+        if f0_method == "fcpe-legacy":
+            return self._fcpe_legacy_f0(np_arr, hop_length).cpu().numpy()
         if f0_method == "rmvpe":
             if self.rmvpe is None:
                 from .rmvpe import RMVPEAMD
@@ -77,8 +85,8 @@ class FeatureInputAMD:
             x = torch.from_numpy(np.copy(np_arr).astype(np.float32)).to(self.device)
             _, f0 = self.crepe[cap].f0_device(x, 0.0)
             return f0.cpu().numpy()
-        raise NotImplementedError(f"f0 method {f0_method!r}: only rmvpe, crepe-*, swipe, fcpe and hybrid[...] over "
-                                  "rmvpe, crepe-*, pm, swipe and fcpe are on the device path")
+        raise NotImplementedError(f"f0 method {f0_method!r}: only rmvpe, crepe-*, swipe, fcpe, fcpe-legacy (with its "
+                                  "model) and hybrid[...] over those and pm are on the device path")
 
     def _dev32(self, np_arr):
         return torch.from_numpy(np.copy(np_arr).astype(np.float32)).to(self.device)
@@ -96,13 +104,31 @@ class FeatureInputAMD:
         return self.fcpe.f0(self._dev32(np_arr), np_arr.size // self.hop, int(hop_length), 0.006, int(self.f0_min),
                             int(self.f0_max))
 
+    def _fcpe_legacy(self, required=True):
+        """The FcpeLegacyAMD held: the one given, or FCPE_LEGACY_PT loaded on first use; without either the method
+        is off the device path (None, or NotImplementedError when ``required``)."""
+        if self.fcpe_legacy is None and os.path.exists(self.FCPE_LEGACY_PT):
+            from .fcpe_legacy import FcpeLegacyAMD
+            self.fcpe_legacy = FcpeLegacyAMD.from_file(self.FCPE_LEGACY_PT, self.device)
+        if self.fcpe_legacy is None and required:
+            raise NotImplementedError(f"f0 method 'fcpe-legacy' needs its model: pass fcpe_legacy=FcpeLegacyAMD(...) "
+                                      f"or provide {self.FCPE_LEGACY_PT}")
+        return self.fcpe_legacy
+
+    def _fcpe_legacy_f0(self, np_arr, hop_length):
+        # get_fcpe(legacy=True) (extract.py:182-189): p_len = x.size // hop, threshold 0.03
+        return self._fcpe_legacy().f0(self._dev32(np_arr), np_arr.size // self.hop, int(hop_length), 0.03)
+
     def compute_f0_hybrid(self, f0_method, np_arr, hop_length=160):
         """extract.py:132-147: the members' raw tracks on the signal as it is (no quantile normalisation, unlike
         the conversion path), each resampled to N // hop frames, then their nanmedian: f64 [N // hop]."""
         from . import f0mix
         p_len = np_arr.size // self.hop
         tracks = []
-        for member in f0mix.parse_hybrid(f0_method, extra=("fcpe",)):
+        extra = ("fcpe",) + (("fcpe-legacy",) if self._fcpe_legacy(required=False) is not None else ())
+        if "fcpe-legacy" in [m.strip() for m in f0_method.partition("[")[2].partition("]")[0].split("+")]:
+            self._fcpe_legacy()  # without the model: raises, saying how to supply it
+        for member in f0mix.parse_hybrid(f0_method, extra=extra):
             if member == "pm":  # get_pm (:153-160): Praat on the f64 samples, zero-padded to N // hop
                 if getattr(self, "pm", None) is None:
                     from .pm import PitchPM
@@ -115,6 +141,8 @@ class FeatureInputAMD:
                 f0 = self._swipe().f0(self._dev32(np_arr))
             elif member == "fcpe":
                 f0 = self._fcpe_f0(np_arr, hop_length)
+            elif member == "fcpe-legacy":
+                f0 = self._fcpe_legacy_f0(np_arr, hop_length)
             else:  # rmvpe f64, crepe-* f32, as compute_f0 returns them
                 f0 = torch.from_numpy(np.ascontiguousarray(self.compute_f0(np_arr, member))).to(self.device)
             tracks.append(f0)

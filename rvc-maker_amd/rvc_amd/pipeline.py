@@ -94,7 +94,7 @@ class VC:
     CREPE_METHODS = {f"crepe-{c}": c for c in ("tiny", "small", "medium", "large", "full")}
     HYBRID_EXTRA = ("fcpe",)  # hybrid members beyond f0mix.MEMBERS: the ones that need a model VC holds
 
-    def __init__(self, tgt_sr, config, rmvpe=None, crepe=None, fcpe=None):
+    def __init__(self, tgt_sr, config, rmvpe=None, crepe=None, fcpe=None, fcpe_legacy=None):
         self.x_pad = config.x_pad
         self.x_query = config.x_query
         self.x_center = config.x_center
@@ -112,6 +112,7 @@ class VC:
         self.is_half = config.is_half
         self.rmvpe = rmvpe
         self.fcpe = fcpe  # FcpeAMD (loaded on first use otherwise)
+        self.fcpe_legacy = fcpe_legacy  # FcpeLegacyAMD (loaded on first use if its file is there, see _fcpe_legacy)
         # library-created streams (CU-masked) this VC owns: destroyed by close() / at exit, after their work
         self._owned = []
         self._finalizer = weakref.finalize(self, _close_streams, self._owned)
@@ -151,6 +152,28 @@ class VC:
             self.fcpe = FcpeAMD.from_file(os.path.join("assets", "models", "predictors", "fcpe.pt"), self.device)
         return self.fcpe
 
+    FCPE_LEGACY_PT = os.path.join("assets", "models", "predictors", "fcpe_legacy.pt")
+
+    def _fcpe_legacy(self, required=True):
+        """The FcpeLegacyAMD this VC holds: the one it was given, or FCPE_LEGACY_PT loaded on first use.  Without
+        either "fcpe-legacy" is off the device path: None, or NotImplementedError when ``required``."""
+        if self.fcpe_legacy is None and os.path.exists(self.FCPE_LEGACY_PT):
+            from .fcpe_legacy import FcpeLegacyAMD
+            self.fcpe_legacy = FcpeLegacyAMD.from_file(self.FCPE_LEGACY_PT, self.device)
+        if self.fcpe_legacy is None and required:
+            raise NotImplementedError(f"f0 method 'fcpe-legacy' needs its model: pass fcpe_legacy=FcpeLegacyAMD(...) "
+                                      f"or provide {self.FCPE_LEGACY_PT}")
+        return self.fcpe_legacy
+
+    def _hybrid_extra(self, f0_method=""):
+        """The hybrid members beyond f0mix.MEMBERS: "fcpe-legacy" only while its model is at hand (a hybrid that
+        names it without one raises here, saying how to supply the model)."""
+        if self._fcpe_legacy(required=False) is not None:
+            return self.HYBRID_EXTRA + ("fcpe-legacy",)
+        if "fcpe-legacy" in [m.strip() for m in f0_method.partition("[")[2].partition("]")[0].split("+")]:
+            self._fcpe_legacy()
+        return self.HYBRID_EXTRA
+
     def _crepe(self, capacity):
         if capacity not in self.crepe:
             from .crepe import CrepeAMD
@@ -163,7 +186,7 @@ class VC:
         """VC.get_f0 (convert.py:304-323) on the device: (coarse int64 [T], pitchf f32 [T]).  Autotune
         and the f0-file override run inside the decode kernels, in the reference's order.  "pm" reads the
         f64 signal ``xp64`` (the reference hands parselmouth the f64 filtfilt output); ``hop_length`` is the one
-        ``pipeline`` receives, which only "fcpe" (alone or as a hybrid member) reads."""
+        ``pipeline`` receives, which only "fcpe" and "fcpe-legacy" (alone or as hybrid members) read."""
         post = None
         if f0_autotune or inp_f0 is not None:
             rep, off = f0_override(inp_f0, self.x_pad) if inp_f0 is not None else (None, 0)
@@ -189,11 +212,15 @@ class VC:
             return self._fcpe().f0_device(xp.contiguous(), float(pitch), xp.numel() // self.window, post=post,
                                           hop_length=int(hop_length), f0_min=int(self.f0_min),
                                           f0_max=int(self.f0_max))
+        if f0_method == "fcpe-legacy":
+            # get_f0_fcpe(legacy=True): threshold 0.03; FCPE_LEGACY never reads f0_min / f0_max
+            return self._fcpe_legacy().f0_device(xp.contiguous(), float(pitch), xp.numel() // self.window, post=post,
+                                                 hop_length=int(hop_length))
         if f0mix.is_hybrid(f0_method):
-            return self._f0_hybrid(xp, float(pitch), f0mix.parse_hybrid(f0_method, extra=self.HYBRID_EXTRA), post,
-                                   hop_length)
-        raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe, fcpe and hybrid[...] over "
-                                  "them are on the MI355X path")
+            members = f0mix.parse_hybrid(f0_method, extra=self._hybrid_extra(f0_method))
+            return self._f0_hybrid(xp, float(pitch), members, post, hop_length)
+        raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe, fcpe, fcpe-legacy (with its "
+                                  "model) and hybrid[...] over them are on the MI355X path")
 
     def _swipe(self, device):
         if getattr(self, "swipe", None) is None:
@@ -204,7 +231,7 @@ class VC:
     def f0_raw(self, x32, member, p_len, hop_length=64):
         """One estimator's raw track (before any shift / autotune) on the device f32 signal x32, as
         get_f0_hybrid's members return it: rmvpe f64 [1 + N//160], crepe-* f32 [1 + N//160], pm f64 padded to
-        p_len, swipe f32 [1 + N//160], fcpe f64 [p_len]."""
+        p_len, swipe f32 [1 + N//160], fcpe and fcpe-legacy f64 [p_len]."""
         if member == "rmvpe":
             return self._rmvpe().f0_device(x32, 0.03, 0.0, want_f0=True)[2]
         if member in self.CREPE_METHODS:
@@ -223,8 +250,10 @@ class VC:
             return self._swipe(x32.device).f0(x32)
         if member == "fcpe":
             return self._fcpe().f0(x32, p_len, int(hop_length), 0.006, int(self.f0_min), int(self.f0_max))
-        raise NotImplementedError(f"hybrid f0 member {member!r}: rmvpe, crepe-*, pm, swipe and fcpe are on the "
-                                  "MI355X path")
+        if member == "fcpe-legacy":
+            return self._fcpe_legacy().f0(x32, p_len, int(hop_length), 0.03)
+        raise NotImplementedError(f"hybrid f0 member {member!r}: rmvpe, crepe-*, pm, swipe, fcpe and fcpe-legacy "
+                                  "(with its model) are on the MI355X path")
 
     def _f0_hybrid(self, xp, pitch, members, post, hop_length=64):
         """get_f0_hybrid + get_f0's post (convert.py:283-323): every member reads the f32 signal divided by its
@@ -735,10 +764,12 @@ class VC:
             raise NotImplementedError("f0_onnx: ONNX f0 models are not on the MI355X path")
         if f0mix.is_hybrid(f0_method):
             # raises, naming the member, for one that is not on the device path
-            f0mix.parse_hybrid(f0_method, extra=self.HYBRID_EXTRA)
+            f0mix.parse_hybrid(f0_method, extra=self._hybrid_extra(f0_method))
+        elif f0_method == "fcpe-legacy":
+            self._fcpe_legacy()  # raises, saying how to supply the model, when there is none
         elif f0_method not in ("rmvpe", "pm", "swipe", "fcpe") and f0_method not in self.CREPE_METHODS:
-            raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe, fcpe and hybrid[...] "
-                                      "over them are on the MI355X path")
+            raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe, fcpe, fcpe-legacy (with "
+                                      "its model) and hybrid[...] over them are on the MI355X path")
         index = None
         if file_index != "" and os.path.exists(file_index) and index_rate != 0:  # convert.py:392-399
             index = self._index(file_index)

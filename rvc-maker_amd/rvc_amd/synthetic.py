@@ -469,6 +469,70 @@ def fcpe_checkpoint(seed: int = 2028, n_layers: int = 6, hidden_dims: int = 512,
     return {"config_dict": {"mel": dict(FCPE_MEL), "model": model}, "model": sd}
 
 
+# gains of the synthetic FCPE_LEGACY (tests/golden/make_golden_fcpe_legacy.py asserts what the fixtures need): the
+# first conv's zero-mean taps are scaled so that the frames differ, dense_out so that the argmax moves, and the
+# output bias puts the legacy threshold (0.03) inside the range the top latent covers
+FCPE_LEGACY_IN_GAIN, FCPE_LEGACY_BODY_GAIN, FCPE_LEGACY_OUT_GAIN, FCPE_LEGACY_OUT_BIAS = 3.0, 0.15, 3.0, -12.8
+FCPE_LEGACY_FEATURES = 266  # int(64 * ln 64), FastAttention's default
+
+
+def fcpe_legacy_checkpoint(seed: int = 3031, n_layers: int = 6, n_chans: int = 512,
+                           nb_features: int = FCPE_LEGACY_FEATURES, out_bias: float = FCPE_LEGACY_OUT_BIAS) -> dict:
+    """A seeded ``fcpe_legacy.pt`` in the reference's layout (FCPE.py:778-782): {"config": {"model", "loss"},
+    "model": FCPE_LEGACY.state_dict()} (tests/golden/fcpe_legacy_keys.json lists the keys).  The Performer
+    projections [nb_features][64] (Gaussian rows made orthogonal in blocks of 64, as FastAttention draws them) are
+    weights: drawn once from the seed."""
+    g = _Gen(seed)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    C, f0_min, f0_max, inner = n_chans, 32.70, 1975.5, 512
+    cents = [1200 * torch.log2(torch.Tensor([f]) / 10)[0] for f in (f0_min, f0_max)]
+    sd["cent_table"] = torch.from_numpy(np.linspace(float(cents[0]), float(cents[1]), 360).astype(np.float32))
+
+    def norm(name):
+        sd[name + ".weight"] = g.uniform((C,), 0.7, 1.3)
+        sd[name + ".bias"] = g.normal((C,), 0.1)
+
+    def linear(name, co, ci, gain=1.0):
+        sd[name + ".weight"] = g.normal((co, ci), gain / math.sqrt(ci))
+        sd[name + ".bias"] = g.normal((co,), 0.02)
+
+    def projection():
+        blocks = []
+        for r0 in range(0, nb_features, 64):
+            qm, _ = np.linalg.qr(g.rng.standard_normal((64, 64)))
+            blocks.append(qm.T[:min(64, nb_features - r0)])
+        scale = np.linalg.norm(g.rng.standard_normal((nb_features, 64)), axis=1)
+        return torch.from_numpy((scale[:, None] * np.concatenate(blocks)).astype(np.float32))
+
+    _conv(g, sd, "stack.0", C, 128, 3, gain=FCPE_LEGACY_IN_GAIN)
+    sd["stack.0.weight"] -= sd["stack.0.weight"].mean(dim=2, keepdim=True)  # see fcpe_checkpoint
+    norm("stack.1")
+    _conv(g, sd, "stack.3", C, C, 3)
+    for i in range(n_layers):
+        p = f"decoder._layers.{i}."
+        norm(p + "conformer.net.0")
+        _conv(g, sd, p + "conformer.net.2", 4 * C, C, 1)
+        _conv(g, sd, p + "conformer.net.4.conv", 2 * C, 1, 31)
+        _conv(g, sd, p + "conformer.net.6", C, 2 * C, 1, gain=FCPE_LEGACY_BODY_GAIN)
+        norm(p + "norm")
+        sd[p + "attn.fast_attention.projection_matrix"] = projection()
+        linear(p + "attn.to_q", inner, C)
+        linear(p + "attn.to_k", inner, C)
+        linear(p + "attn.to_v", inner, C)
+        linear(p + "attn.to_out", C, inner, gain=FCPE_LEGACY_BODY_GAIN)
+    norm("norm")
+    sd["dense_out.bias"] = g.normal((360,), 0.5) + out_bias
+    v = g.normal((360, C), 1.0 / math.sqrt(C))
+    sd["dense_out.parametrizations.weight.original0"] = \
+        v.pow(2).sum(dim=1, keepdim=True).sqrt() * g.uniform((360, 1), 0.7, 1.3) * FCPE_LEGACY_OUT_GAIN
+    sd["dense_out.parametrizations.weight.original1"] = v
+    model = {"input_channel": 128, "out_dims": 360, "n_layers": n_layers, "n_chans": C, "use_siren": False,
+             "use_full": False, "confidence": False, "threshold": 0.05, "use_input_conv": True}
+    loss = {"loss_mse_scale": 10, "loss_l2_regularization": False, "loss_l2_regularization_scale": 1,
+            "loss_grad1_mse": False, "loss_grad1_mse_scale": 1}
+    return {"config": {"model": model, "loss": loss}, "model": sd}
+
+
 # ---------------------------------------------------------------- audio
 def synthetic_audio(seconds: float, seed: int = 1000, sr: int = 16000) -> np.ndarray:
     """SURVEY §8(d) test signal: 3-harmonic glide (60-240 Hz) + 200 ms gaps every 5 s + noise, peak <= 0.9."""

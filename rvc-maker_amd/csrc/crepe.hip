@@ -200,11 +200,7 @@ __global__ __launch_bounds__(256) void crepe_smooth_coarse_kernel(const float* f
     }
     if (!isinf(med) && med < 0.1f) f = 0.f;  // an infinite median becomes NaN in the reference: kept
     f = f0_post_apply<float>(f, t, shift, post);
-    float mel = 1127.f * logf(1.f + f / 700.f);
-    if (mel > 0.f) mel = (float)(((double)mel - mel_min) * 254.0 / (mel_max - mel_min) + 1.0);
-    if (mel <= 1.f) mel = 1.f;
-    if (mel > 255.f) mel = 255.f;
-    coarse[t] = (int64_t)rintf(mel);
+    coarse[t] = f0_coarse(f, mel_min, mel_max);
     pitchf[t] = f;
 }
 }  // namespace

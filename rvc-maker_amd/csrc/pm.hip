@@ -357,11 +357,7 @@ __global__ void pm_post_kernel(const double* f0, int64_t nf, int64_t nout, int64
     const int64_t s = t - pad;
     double v = (s >= 0 && s < nf) ? f0[s] : 0.0;
     v = f0_post_apply<double>(v, t, shift, post);
-    double fm = 1127.0 * log(1.0 + v / 700.0);
-    if (fm > 0) fm = (fm - mel_min) * 254.0 / (mel_max - mel_min) + 1.0;
-    if (fm <= 1) fm = 1;
-    if (fm > 255) fm = 255;
-    coarse[t] = (int64_t)rint(fm);
+    coarse[t] = f0_coarse(v, mel_min, mel_max);
     pitchf[t] = (float)v;
 }
 
@@ -431,9 +427,9 @@ extern "C" int rvc_pm_post(const double* f0, int64_t nf, int64_t p_len, double s
     const int64_t pad = padded ? (p_len - nf + 1) / 2 : 0;
     const int64_t nout = padded ? p_len : nf;
     const rvc_f0_post pp = f0_post_or_none(post);
-    const double mel_min = 1127.0 * log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * log(1.0 + 1100.0 / 700.0);
+    const F0MelRange mel = f0_mel_range();
     hipLaunchKernelGGL(pm_post_kernel, dim3(cdiv(nout, 256)), dim3(256), 0, (hipStream_t)stream, f0, nf, nout,
-                       pad, shift, mel_min, mel_max, pp, coarse, pitchf);
+                       pad, shift, mel.min, mel.max, pp, coarse, pitchf);
     RVC_HIP(hipGetLastError());
     return RVC_OK;
 }

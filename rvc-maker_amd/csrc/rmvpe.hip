@@ -417,11 +417,7 @@ __global__ void rmvpe_decode_kernel(const float* sal, int64_t ld, int64_t F, dou
     if (f0 == 10.0) f0 = 0.0;
     f0 = f0_post_apply<double>(f0, t, shift, post);
     if (f0_out) f0_out[t] = f0;
-    double fm = 1127.0 * log(1.0 + f0 / 700.0);
-    if (fm > 0) fm = (fm - mel_min) * 254.0 / (mel_max - mel_min) + 1.0;
-    if (fm <= 1) fm = 1;
-    if (fm > 255) fm = 255;
-    coarse[t] = (int64_t)rint(fm);
+    coarse[t] = f0_coarse(f0, mel_min, mel_max);
     pitchf[t] = (float)f0;
 }
 
@@ -431,9 +427,9 @@ extern "C" int rvc_rmvpe_decode(const float* sal, int64_t ld, int64_t F, double 
     RVC_CHECK_ARG(sal && coarse && pitchf && F > 0 && ld >= F, "rmvpe_decode: bad args");
     RVC_CHECK_ARG(!post || !post->rep || (post->rep_off >= 0 && post->rep_len >= 0), "rmvpe_decode: bad f0 post");
     const rvc_f0_post pp = f0_post_or_none(post);
-    const double mel_min = 1127.0 * log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * log(1.0 + 1100.0 / 700.0);
+    const F0MelRange mel = f0_mel_range();
     hipLaunchKernelGGL(rmvpe_decode_kernel, dim3(cdiv(F, 128)), dim3(128), 0, (hipStream_t)stream, sal, ld, F, thred,
-                       shift, mel_min, mel_max, pp, f0, coarse, pitchf);
+                       shift, mel.min, mel.max, pp, f0, coarse, pitchf);
     RVC_HIP(hipGetLastError());
     return RVC_OK;
 }

@@ -137,6 +137,34 @@ RVC_DEV F f0_post_apply(F f, int64_t t, F shift, const rvc_f0_post& post) {
     return f;
 }
 
+// get_f0's quantiser (convert.py:319-323): mel = 1127 log(1 + f0 / 700); mel > 0 mapped affinely onto 1..255 over
+// [mel_min, mel_max]; clamp [1, 255]; rint.  The f64 form is what NumPy computes on an f64 f0 array (rmvpe, pm, fcpe,
+// hybrids).  On an f32 array (crepe, swipe) the mel stays f32 and the f64 mel_min / mel_max scalars promote only the
+// affine step, whose result is stored back into the f32 array.
+RVC_DEV int64_t f0_coarse(double f0, double mel_min, double mel_max) {
+    double fm = 1127.0 * log(1.0 + f0 / 700.0);
+    if (fm > 0) fm = (fm - mel_min) * 254.0 / (mel_max - mel_min) + 1.0;
+    if (fm <= 1) fm = 1;
+    if (fm > 255) fm = 255;
+    return (int64_t)rint(fm);
+}
+
+RVC_DEV int64_t f0_coarse(float f0, double mel_min, double mel_max) {
+    float mel = 1127.f * logf(1.f + f0 / 700.f);
+    if (mel > 0.f) mel = (float)(((double)mel - mel_min) * 254.0 / (mel_max - mel_min) + 1.0);
+    if (mel <= 1.f) mel = 1.f;
+    if (mel > 255.f) mel = 255.f;
+    return (int64_t)rintf(mel);
+}
+
+// the quantiser's range on the host: the mel of VC's f0_min = 50 Hz and f0_max = 1100 Hz
+struct F0MelRange {
+    double min, max;
+};
+static inline F0MelRange f0_mel_range() {
+    return {1127.0 * log(1.0 + 50.0 / 700.0), 1127.0 * log(1.0 + 1100.0 / 700.0)};
+}
+
 static inline rvc_f0_post f0_post_or_none(const rvc_f0_post* p) {
     rvc_f0_post z = {};
     return p ? *p : z;

@@ -565,11 +565,7 @@ __global__ __launch_bounds__(256) void sw_post_kernel(const float* f0, int64_t F
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= F) return;
     const float f = f0_post_apply<float>(f0[k], k, shift, post);
-    float mel = 1127.f * logf(1.f + f / 700.f);
-    if (mel > 0.f) mel = (float)(((double)mel - mel_min) * 254.0 / (mel_max - mel_min) + 1.0);
-    if (mel <= 1.f) mel = 1.f;
-    if (mel > 255.f) mel = 255.f;
-    coarse[k] = (int64_t)rintf(mel);
+    coarse[k] = f0_coarse(f, mel_min, mel_max);
     pitchf[k] = f;
 }
 
@@ -695,9 +691,9 @@ extern "C" int rvc_swipe_post(const float* f0, int64_t F, float shift, const rvc
                               float* pitchf, rvc_stream_t stream) {
     RVC_CHECK_ARG(f0 && coarse && pitchf && F > 0, "swipe_post: bad args");
     RVC_CHECK_ARG(!post || !post->rep || (post->rep_off >= 0 && post->rep_len >= 0), "swipe_post: bad f0 post");
-    const double mel_min = 1127.0 * log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * log(1.0 + 1100.0 / 700.0);
-    hipLaunchKernelGGL(sw_post_kernel, dim3(cdiv(F, 256)), dim3(256), 0, (hipStream_t)stream, f0, F, shift, mel_min,
-                       mel_max, f0_post_or_none(post), coarse, pitchf);
+    const F0MelRange mel = f0_mel_range();
+    hipLaunchKernelGGL(sw_post_kernel, dim3(cdiv(F, 256)), dim3(256), 0, (hipStream_t)stream, f0, F, shift, mel.min,
+                       mel.max, f0_post_or_none(post), coarse, pitchf);
     RVC_HIP(hipGetLastError());
     return RVC_OK;
 }

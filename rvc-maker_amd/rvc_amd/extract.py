@@ -15,9 +15,10 @@ the file list.  Host-side steps (coarse quantiser, file naming, list building) f
 expression for expression; ``tests/golden/edges.npz`` pins ``coarse_f0`` against it.
 
 f0 methods on the device: ``rmvpe``, ``crepe-{tiny,...,full}``, ``swipe``, ``fcpe``, ``fcpe-legacy`` (when its
-model is given or ``assets/models/predictors/fcpe_legacy.pt`` exists) and ``hybrid[a+b+...]`` over those and ``pm``
+model is given or ``FeatureInputAMD.FCPE_LEGACY_PT`` exists) and ``hybrid[a+b+...]`` over those and ``pm``
 (the reference's other estimators -- harvest, dio, yin, pyin, ... -- are third-party or off the path and
-raise).  Embedders: fairseq
+raise).  The estimators, their loaders and the members' raw tracks are f0.py's ``F0Bank``, shared with the
+conversion path's ``VC``; ``compute_f0`` copies the signal to the device and the track back.  Embedders: fairseq
 ContentVec (``embedders_mode="fairseq"``).
 """
 from __future__ import annotations
@@ -31,14 +32,15 @@ import numpy as np
 import torch
 
 from . import audio_io, ops
+from .f0 import F0Bank
 
 log = logging.getLogger(__name__)
 
 
-class FeatureInputAMD:
+class FeatureInputAMD(F0Bank):
     """extract.py:120-243 with the f0 estimators on the device."""
 
-    FCPE_LEGACY_PT = os.path.join("assets", "models", "predictors", "fcpe_legacy.pt")
+    MEMBER_ONLY = ("pm",)  # get_pm feeds hybrids here; alone it is not on this path
 
     def __init__(self, sample_rate=16000, hop_size=160, device="cuda:0", rmvpe=None, crepe=None, fcpe=None,
                  fcpe_legacy=None):
@@ -50,103 +52,38 @@ class FeatureInputAMD:
         self.f0_mel_min = 1127 * np.log(1 + self.f0_min / 700)
         self.f0_mel_max = 1127 * np.log(1 + self.f0_max / 700)
         self.device = device
-        self.rmvpe = rmvpe
-        self.crepe = dict(crepe or {})
-        self.fcpe = fcpe
-        self.fcpe_legacy = fcpe_legacy
+        self._init_f0(rmvpe, crepe, fcpe, fcpe_legacy)
 
     def compute_f0(self, np_arr, f0_method, hop_length=160, f0_onnx=False):
-        """extract.py:149-151 for the device methods: rmvpe -> f64 [1 + N//160] (RMVPE.infer_from_audio,
-        thred 0.03); crepe-<cap> -> f32 [1 + N//160] (get_crepe, :173-180); fcpe -> f64 [N // 160] (get_fcpe,
-        :182-188; fcpe-legacy the same with legacy=True, threshold 0.03: the two methods that read
-        ``hop_length``)."""
+        """extract.py:149-151 for the device methods, each as F0Bank.f0_raw returns it, on the host: rmvpe f64
+        [1 + N//160] (RMVPE.infer_from_audio, thred 0.03), crepe-<cap> and swipe f32 [1 + N//160], fcpe and fcpe-legacy
+        f64 [N // 160] (the two that read ``hop_length``); hybrid[...] see compute_f0_hybrid."""
         if f0_onnx:
             raise NotImplementedError(f"f0 method {f0_method!r} (onnx) is not on the device path")
+        self.check_f0_method(f0_method)  # raises for what is not on the device path, before any device work
         if "hybrid" in f0_method:
             return self.compute_f0_hybrid(f0_method, np_arr, hop_length)
-        if f0_method == "swipe":  # get_swipe (:212-216): f32 [1 + N//160]
-            return self._swipe().f0(self._dev32(np_arr)).cpu().numpy()
-        if f0_method == "fcpe":
-            return self._fcpe_f0(np_arr, hop_length).cpu().numpy()
-        if f0_method == "fcpe-legacy":
-            return self._fcpe_legacy_f0(np_arr, hop_length).cpu().numpy()
+        f0 = self.f0_raw(self._dev32(np_arr), f0_method, np_arr.size // self.hop, hop_length).cpu().numpy()
         if f0_method == "rmvpe":
-            if self.rmvpe is None:
-                from .rmvpe import RMVPEAMD
-                self.rmvpe = RMVPEAMD.from_file(os.path.join("assets", "models", "predictors", "rmvpe.pt"),
-                                                self.device)
-            return self.rmvpe.infer_from_audio(np_arr, thred=0.03)
-        if f0_method.startswith("crepe-"):
-            cap = f0_method.split("-", 1)[1]
-            if cap not in self.crepe:
-                from .crepe import CrepeAMD
-                self.crepe[cap] = CrepeAMD.from_file(
-                    os.path.join("assets", "models", "predictors", f"crepe_{cap}.pth"), cap, self.device)
-            x = torch.from_numpy(np.copy(np_arr).astype(np.float32)).to(self.device)
-            _, f0 = self.crepe[cap].f0_device(x, 0.0)
-            return f0.cpu().numpy()
-        raise NotImplementedError(f"f0 method {f0_method!r}: only rmvpe, crepe-*, swipe, fcpe, fcpe-legacy (with its "
-                                  "model) and hybrid[...] over those and pm are on the device path")
+            self.rmvpe.check_error()  # the BiGRU's hand-off timeout, as RMVPE.infer_from_audio checks it
+        return f0
 
     def _dev32(self, np_arr):
         return torch.from_numpy(np.copy(np_arr).astype(np.float32)).to(self.device)
 
-    def _swipe(self):
-        if getattr(self, "swipe", None) is None:
-            from .swipe import SwipeAMD
-            self.swipe = SwipeAMD(self.device)
-        return self.swipe
-
-    def _fcpe_f0(self, np_arr, hop_length):
-        if self.fcpe is None:
-            from .fcpe import FcpeAMD
-            self.fcpe = FcpeAMD.from_file(os.path.join("assets", "models", "predictors", "fcpe.pt"), self.device)
-        return self.fcpe.f0(self._dev32(np_arr), np_arr.size // self.hop, int(hop_length), 0.006, int(self.f0_min),
-                            int(self.f0_max))
-
-    def _fcpe_legacy(self, required=True):
-        """The FcpeLegacyAMD held: the one given, or FCPE_LEGACY_PT loaded on first use; without either the method
-        is off the device path (None, or NotImplementedError when ``required``)."""
-        if self.fcpe_legacy is None and os.path.exists(self.FCPE_LEGACY_PT):
-            from .fcpe_legacy import FcpeLegacyAMD
-            self.fcpe_legacy = FcpeLegacyAMD.from_file(self.FCPE_LEGACY_PT, self.device)
-        if self.fcpe_legacy is None and required:
-            raise NotImplementedError(f"f0 method 'fcpe-legacy' needs its model: pass fcpe_legacy=FcpeLegacyAMD(...) "
-                                      f"or provide {self.FCPE_LEGACY_PT}")
-        return self.fcpe_legacy
-
-    def _fcpe_legacy_f0(self, np_arr, hop_length):
-        # get_fcpe(legacy=True) (extract.py:182-189): p_len = x.size // hop, threshold 0.03
-        return self._fcpe_legacy().f0(self._dev32(np_arr), np_arr.size // self.hop, int(hop_length), 0.03)
-
     def compute_f0_hybrid(self, f0_method, np_arr, hop_length=160):
         """extract.py:132-147: the members' raw tracks on the signal as it is (no quantile normalisation, unlike
-        the conversion path), each resampled to N // hop frames, then their nanmedian: f64 [N // hop]."""
+        the conversion path; get_pm reads the f64 samples), each resampled to N // hop frames, then their nanmedian:
+        f64 [N // hop]."""
         from . import f0mix
+        members = self.f0_members(f0_method)
         p_len = np_arr.size // self.hop
-        tracks = []
-        extra = ("fcpe",) + (("fcpe-legacy",) if self._fcpe_legacy(required=False) is not None else ())
-        if "fcpe-legacy" in [m.strip() for m in f0_method.partition("[")[2].partition("]")[0].split("+")]:
-            self._fcpe_legacy()  # without the model: raises, saying how to supply it
-        for member in f0mix.parse_hybrid(f0_method, extra=extra):
-            if member == "pm":  # get_pm (:153-160): Praat on the f64 samples, zero-padded to N // hop
-                if getattr(self, "pm", None) is None:
-                    from .pm import PitchPM
-                    self.pm = PitchPM(self.device)
-                f0 = self.pm.to_pitch_ac(torch.from_numpy(np.asarray(np_arr, np.float64)).to(self.device))
-                pad = (p_len - f0.numel() + 1) // 2
-                if pad > 0 or p_len - f0.numel() - pad > 0:
-                    f0 = torch.nn.functional.pad(f0, (pad, p_len - f0.numel() - pad))
-            elif member == "swipe":
-                f0 = self._swipe().f0(self._dev32(np_arr))
-            elif member == "fcpe":
-                f0 = self._fcpe_f0(np_arr, hop_length)
-            elif member == "fcpe-legacy":
-                f0 = self._fcpe_legacy_f0(np_arr, hop_length)
-            else:  # rmvpe f64, crepe-* f32, as compute_f0 returns them
-                f0 = torch.from_numpy(np.ascontiguousarray(self.compute_f0(np_arr, member))).to(self.device)
-            tracks.append(f0)
-        return f0mix.mix(tracks, p_len).cpu().numpy()
+        x32 = self._dev32(np_arr)
+        x64 = torch.from_numpy(np.asarray(np_arr, np.float64)).to(self.device) if "pm" in members else None
+        f0 = f0mix.mix([self.f0_raw(x32, m, p_len, hop_length, x64) for m in members], p_len).cpu().numpy()
+        if "rmvpe" in members:
+            self.rmvpe.check_error()
+        return f0
 
     def coarse_f0(self, f0):
         """extract.py:225-226 (numpy, same expression and dtype promotion)."""

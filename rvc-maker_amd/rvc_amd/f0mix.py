@@ -1,5 +1,7 @@
 """hybrid[a+b+...] f0 (``VC.get_f0_hybrid``, main/inference/convert.py:283-302) on the device (csrc/f0mix.hip):
 the 0.999 |x| quantile normalisation of the members' input and the resample-and-median mix of their raw tracks.
+Which members exist and what each returns is f0.py's (``F0Bank.f0_members``, ``F0Bank.f0_raw``); ``parse_hybrid`` is the
+one parser of the method string.
 """
 from __future__ import annotations
 
@@ -8,10 +10,10 @@ import re
 
 import torch
 
-from . import _lib, ops
+from . import _lib, f0, ops
 
-CREPE_MEMBERS = ("crepe-tiny", "crepe-small", "crepe-medium", "crepe-large", "crepe-full")
-MEMBERS = ("rmvpe", "pm", "swipe") + CREPE_MEMBERS
+CREPE_MEMBERS = tuple(f0.CREPE_METHODS)
+MEMBERS = ("rmvpe", "pm", "swipe") + CREPE_MEMBERS  # the members that need no model, or one every holder can load
 MAX_TRACKS = 8
 
 
@@ -22,16 +24,15 @@ def is_hybrid(f0_method: str) -> bool:
 def parse_hybrid(f0_method: str, extra=()) -> list[str]:
     """"hybrid[a+b]" -> ["a", "b"] as get_f0_hybrid parses it; a member that is not on the device path raises
     NotImplementedError naming it.  A repeated member stays repeated (the reference computes it again).
-    ``extra`` names members the caller accepts beyond MEMBERS (VC and FeatureInputAMD pass ("fcpe",): they hold
-    the model it needs)."""
+    ``extra`` names members the caller accepts beyond MEMBERS (f0.F0Bank.f0_members passes the ones whose model it
+    holds: "fcpe", and "fcpe-legacy", whose model it then asks for)."""
     m = re.search(r"hybrid\[(.+)\]", f0_method)
     if not m:
         raise ValueError(f"f0 method {f0_method!r}: expected hybrid[a+b+...]")
     members = [s.strip() for s in m.group(1).split("+")]
     for name in members:
         if name not in MEMBERS and name not in extra:
-            raise NotImplementedError(f"hybrid f0 member {name!r}: rmvpe, crepe-*, pm and swipe are on the "
-                                      "MI355X path")
+            f0.refuse("hybrid f0 member", name)
     if len(members) > MAX_TRACKS:
         raise NotImplementedError(f"hybrid f0: {len(members)} members (at most {MAX_TRACKS})")
     return members

@@ -1,9 +1,12 @@
 """fcpe-legacy f0 on the device: ``VC.get_f0_fcpe(legacy=True)`` (main/inference/convert.py:239-246) -- the
 Performer-attention ``FCPE_LEGACY`` of main/library/predictors/FCPE.py behind ``Wav2Mel``, at 16 kHz and threshold
-0.03 -- followed by get_f0's shift / autotune / f0 file / mel quantiser (``rvc_pm_post``).
+0.03 -- followed by get_f0's shift / autotune / f0 file / mel quantiser (``ops.f0_post64``).
 
 The mel front end, GroupNorm, the Conformer conv module, the local-argmax decoder and the post-processing are
-fcpe's (csrc/fcpe.hip: ``Wav2Mel`` computes what ``Wav2MelModule`` does, bit for bit); what the legacy model adds is
+fcpe's (csrc/fcpe.hip: ``Wav2Mel`` computes what ``Wav2MelModule`` does, bit for bit), and so is the code that runs
+them: ``FcpeLegacyAMD`` is ``FcpeAMD`` with FCPE_LEGACY's checkpoint names, its config checks, the attention weights
+and buffers, the layer order and the open f0 range; constructor, stem, conformer, head and ``f0_device`` are
+inherited.  What the legacy model adds is
 12 layers of FAVOR+ linear self-attention, csrc/performer.hip.  Per layer (``_EncoderLayer.forward``, FCPE.py:387-389):
 x + to_out(performer(to_q, to_k, to_v of LayerNorm(x))), then x + conformer(x).  The three input linears are one
 1x1 conv C -> 1536 whose output the kernel reads in place, and ``to_out`` takes the residual in its epilogue; the
@@ -18,9 +21,9 @@ import ctypes
 
 import torch
 
-from . import _lib, melbasis, ops
-from .fcpe import PRECISION, FcpeAMD, _pv
-from .ops import ACT_SIGMOID, Conv
+from . import _lib, ops
+from .fcpe import FcpeAMD
+from .ops import Conv, _p
 
 HEADS, DIM_HEAD = 8, 64  # SelfAttention's defaults (FCPE.py:586): PCmer builds every layer with them
 INNER = HEADS * DIM_HEAD
@@ -48,61 +51,30 @@ def _check_config(cfg, sd):
 
 
 class FcpeLegacyAMD(FcpeAMD):
-    def __init__(self, ckpt: dict, device="cuda"):
-        model = _check_config(ckpt["config"], ckpt["model"])
-        sd = {k: v.float() for k, v in ckpt["model"].items()}
-        self.device = device
-        self.C, self.n_layers = int(model["n_chans"]), int(model["n_layers"])
-        C = self.C
-        if sd["stack.0.weight"].shape != (C, 128, 3) or C % 4 or C > 2048:
-            raise ValueError(f"fcpe-legacy: n_chans {C} does not match the checkpoint")
+    NAME, CONFIG, CHANS = "fcpe-legacy", "config", "n_chans"
+    STEM, LAYER, OUT = "stack.", "decoder._layers.{}.", "dense_out."
+    THRESHOLD = 0.03
 
-        def dev(name):
-            return sd[name].contiguous().to(device)
+    _check_config = staticmethod(_check_config)
+
+    def _layer_weights(self, sd, prefix):
+        n, a = prefix + "norm.", prefix + "attn."
+        if sd[a + "to_q.weight"].shape != (INNER, self.C):
+            raise NotImplementedError(f"fcpe-legacy: to_q {tuple(sd[a + 'to_q.weight'].shape)} ({HEADS} heads of "
+                                      f"{DIM_HEAD} are on the MI355X path)")
 
         def linear(names):
-            w = torch.cat([sd[n + ".weight"] for n in names])
-            return Conv(w.unsqueeze(-1).contiguous(), torch.cat([sd[n + ".bias"] for n in names]), device=device)
+            w = torch.cat([sd[a + k + ".weight"] for k in names])
+            return Conv(w.unsqueeze(-1).contiguous(), torch.cat([sd[a + k + ".bias"] for k in names]),
+                        device=self.device)
 
-        self.basis = torch.from_numpy(melbasis.mel_filterbank(16000, 1024, 128, 0, 8000, htk=False)).to(device)
-        self.conv0 = Conv(sd["stack.0.weight"], sd["stack.0.bias"], device=device)
-        self.gn = (dev("stack.1.weight"), dev("stack.1.bias"))
-        self.conv1 = Conv(sd["stack.3.weight"], sd["stack.3.bias"], device=device)
-        self.layers = []
-        for i in range(self.n_layers):
-            n, a, p = (f"decoder._layers.{i}.{s}" for s in ("norm.", "attn.", "conformer.net."))
-            dw = sd[p + "4.conv.weight"]
-            if dw.shape[1] != 1 or dw.shape[2] % 2 == 0 or dw.shape[2] > 31:
-                raise NotImplementedError(f"fcpe-legacy: depthwise kernel {tuple(dw.shape)}")
-            if sd[a + "to_q.weight"].shape != (INNER, C):
-                raise NotImplementedError(f"fcpe-legacy: to_q {tuple(sd[a + 'to_q.weight'].shape)} ({HEADS} heads of "
-                                          f"{DIM_HEAD} are on the MI355X path)")
-            self.layers.append(dict(norm=(dev(n + "weight"), dev(n + "bias")),
-                                    qkv=linear([a + "to_q", a + "to_k", a + "to_v"]),
-                                    proj=dev(a + "fast_attention.projection_matrix"),
-                                    to_out=linear([a + "to_out"]),
-                                    ln=(dev(p + "0.weight"), dev(p + "0.bias")),
-                                    up=Conv(sd[p + "2.weight"], sd[p + "2.bias"], device=device),
-                                    dw=(dw[:, 0].contiguous().to(device), dev(p + "4.conv.bias"), int(dw.shape[2])),
-                                    down=Conv(sd[p + "6.weight"], sd[p + "6.bias"], device=device)))
-        self.norm = (dev("norm.weight"), dev("norm.bias"))
-        w = torch._weight_norm(sd["dense_out.parametrizations.weight.original1"],
-                               sd["dense_out.parametrizations.weight.original0"], 0)
-        self.proj = Conv(w.unsqueeze(-1).contiguous(), sd["dense_out.bias"], device=device)
-        self.cent_table = dev("cent_table")
-        self._bufs = {}
+        return dict(self._conformer_weights(sd, prefix + "conformer.net."),
+                    norm=(self._dev(sd, n + "weight"), self._dev(sd, n + "bias")),
+                    qkv=linear(["to_q", "to_k", "to_v"]), to_out=linear(["to_out"]),
+                    proj=self._dev(sd, a + "fast_attention.projection_matrix"))
 
-    # ------------------------------------------------------------------ buffers
-    def _buffers(self, T, dev):
-        store = self._bufs if ops._WS_PRIVATE is None else ops._WS_PRIVATE
-        key = f"fcpe_legacy{id(self)}/{T}/{torch.cuda.current_stream(dev).stream_id}"
-        b = store.get(key)
-        if b is None:
-            C = self.C
-            e = lambda *s: torch.empty(*s, device=dev)  # noqa: E731
-            b = store[key] = dict(mel=e(128, T), a=e(C, T), b=e(C, T), n=e(C, T), h=e(4 * C, T), u=e(2 * C, T),
-                                  qkv=e(3 * INNER, T), att=e(INNER, T), latent=e(360, T), f0m=e(T))
-        return b
+    def _extra_buffers(self, T):
+        return dict(qkv=(3 * INNER, T), att=(INNER, T))
 
     # ------------------------------------------------------------------ network
     @staticmethod
@@ -114,9 +86,9 @@ class FcpeLegacyAMD(FcpeAMD):
             raise ValueError(f"fcpe-legacy: bad attention shape T={T} M={M}")
         work = ops._workspace(qkv.device, need, "performer")
         step = INNER * T * 4
-        ops.check(lib.rvc_performer_attention(_pv(qkv), ctypes.c_void_p(qkv.data_ptr() + step),
-                                              ctypes.c_void_p(qkv.data_ptr() + 2 * step), _pv(proj), _pv(out), 1, HEADS,
-                                              T, DIM_HEAD, M, T, 3 * INNER * T, INNER * T, _pv(work), need,
+        ops.check(lib.rvc_performer_attention(_p(qkv), ctypes.c_void_p(qkv.data_ptr() + step),
+                                              ctypes.c_void_p(qkv.data_ptr() + 2 * step), _p(proj), _p(out), 1, HEADS,
+                                              T, DIM_HEAD, M, T, 3 * INNER * T, INNER * T, _p(work), need,
                                               ops._stream()), "performer_attention")
         return out
 
@@ -127,31 +99,12 @@ class FcpeLegacyAMD(FcpeAMD):
         self.performer(buf["qkv"], L["proj"], buf["att"])
         return L["to_out"](buf["att"], out=out, res=res)
 
-    def _latent(self, x32, buf):
-        lib, C, T, dev = _lib.load(), self.C, buf["f0m"].numel(), x32.device
-        self.mel(x32, buf["mel"])
-        with ops.precision(PRECISION):
-            self.conv0(buf["mel"], pad=1, out=buf["a"])
-            need = lib.rvc_groupnorm_work_bytes(1, 4)
-            work = ops._workspace(dev, need, "fcpe_gn")
-            ops.check(lib.rvc_groupnorm_act(_pv(buf["a"]), _pv(self.gn[0]), _pv(self.gn[1]), _pv(buf["b"]), 1, C, T, 4,
-                                            1e-5, 0.01, _pv(work), need, ops._stream()), "groupnorm_act")
-            x, y = buf["a"], buf["b"]
-            self.conv1(y, pad=1, out=x)
-            for L in self.layers:
-                ops.layernorm_cf(x, None, L["norm"][0], L["norm"][1], buf["n"], 1, C, T)
-                self.self_attention(L, buf["n"], buf, y, res=x)
-                x, y = y, x
-                ops.layernorm_cf(x, None, L["ln"][0], L["ln"][1], buf["n"], 1, C, T)
-                L["up"](buf["n"], out=buf["h"])
-                w, b, K = L["dw"]
-                ops.check(lib.rvc_glu_dwconv_silu(_pv(buf["h"]), _pv(w), _pv(b), _pv(buf["u"]), 1, 2 * C, T, K,
-                                                  ops._stream()), "glu_dwconv_silu")
-                L["down"](buf["u"], out=y, res=x)
-                x, y = y, x
-            ops.layernorm_cf(x, None, self.norm[0], self.norm[1], buf["n"], 1, C, T)
-            self.proj(buf["n"], out=buf["latent"], out_act=ACT_SIGMOID)
-        return buf["latent"]
+    def _layer(self, L, x, y, buf):
+        """_EncoderLayer.forward (FCPE.py:387-389): x + attention(LayerNorm(x)), then x + conformer(x)."""
+        C, T = x.shape
+        ops.layernorm_cf(x, None, L["norm"][0], L["norm"][1], buf["n"], 1, C, T)
+        self.self_attention(L, buf["n"], buf, y, res=x)
+        return self._conformer(L, y, x, buf)
 
     # ------------------------------------------------------------------ f0
     def decode(self, latent, threshold=0.03, out=None):
@@ -159,18 +112,9 @@ class FcpeLegacyAMD(FcpeAMD):
         f0 range."""
         return super().decode(latent, threshold, 0.0, F0_OPEN, out=out)
 
-    def f0(self, x32, p_len, hop_length=160, threshold=0.03):
-        """get_f0_fcpe(legacy=True): x32 device f32 [n] at 16 kHz -> f0 f64 [p_len]."""
+    def f0(self, x32, p_len, hop_length=160, threshold=0.03, f0_min=None, f0_max=None):
+        """get_f0_fcpe(legacy=True): x32 device f32 [n] at 16 kHz -> f0 f64 [p_len].  ``f0_min`` / ``f0_max`` are taken
+        as the reference's FCPE(legacy=True) takes them and, as there, never read."""
         buf = self._buffers(self._x32(x32), x32.device)
         self.decode(self._latent(x32, buf), threshold, out=buf["f0m"])
         return self.post(buf["f0m"], p_len, hop_length)
-
-    def f0_device(self, xp, pitch, p_len, post=None, hop_length=160):
-        """get_f0(..., "fcpe-legacy") on the device: (coarse int64 [p_len], pitchf f32 [p_len])."""
-        f0 = self.f0(xp, p_len, hop_length, 0.03)
-        coarse = torch.empty(p_len, dtype=torch.int64, device=xp.device)
-        pitchf = torch.empty(p_len, dtype=torch.float32, device=xp.device)
-        ops.check(_lib.load().rvc_pm_post(_pv(f0), p_len, p_len, float(2.0 ** (pitch / 12)),
-                                          ops._post_ref(post, p_len), _pv(coarse), _pv(pitchf), ops._stream()),
-                  "pm_post")
-        return coarse, pitchf

@@ -22,7 +22,7 @@ def _stream():
 def _p(t):
     if t is None:
         return None
-    if not t.is_cuda or t.dtype not in (torch.float32, torch.int64, torch.int32):
+    if not t.is_cuda or t.dtype not in (torch.float32, torch.int64, torch.int32, torch.uint8):  # uint8: table blobs
         raise TypeError(f"rvc_amd: expected a CUDA f32/int tensor, got {t.dtype} on {t.device}")
     return ctypes.c_void_p(t.data_ptr())
 
@@ -971,6 +971,20 @@ class F0Post:
 
 def _post_ref(post, F):
     return ctypes.byref(post.struct(F)) if post is not None else None
+
+
+def f0_post64(f0, p_len, pitch, post=None):
+    """get_f0's tail on an f64 track (convert.py:308-323; rvc_pm_post): f0 device f64 [nf], zero-padded in front and
+    behind to p_len when shorter (get_f0_pm's padding), then autotune / shift by ``pitch`` semitones / f0 file / the
+    mel quantiser, all in f64 -> (coarse int64 [nout], pitchf f32 [nout]), nout = max(p_len, nf).  The tail of pm,
+    fcpe, fcpe-legacy and the hybrids; rmvpe, crepe and swipe fuse theirs into their own decode kernels."""
+    nf = f0.numel()
+    nout = max(p_len, nf)
+    coarse = torch.empty(nout, dtype=torch.int64, device=f0.device)
+    pitchf = torch.empty(nout, dtype=torch.float32, device=f0.device)
+    check(_lib.load().rvc_pm_post(_pd(f0), nf, p_len, float(2.0 ** (pitch / 12)), _post_ref(post, nout), _p(coarse),
+                                  _p(pitchf), _stream()), "pm_post")
+    return coarse, pitchf
 
 
 def rmvpe_decode(sal, ld, F, thred, shift, f0, coarse, pitchf, post=None):

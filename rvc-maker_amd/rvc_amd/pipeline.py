@@ -4,8 +4,9 @@
 pitch_guidance, filter_radius, volume_envelope, version, protect, hop_length, f0_autotune,
 f0_autotune_strength, suffix, embed_suffix, f0_file=None, f0_onnx=False, pbar=None)`` keeps the
 reference signature and returns float32 numpy audio at tgt_sr.  ``model`` is a
-``ContentVecAMD`` (``.pt`` embedder), ``net_g`` a ``SynthesizerAMD`` (``.pth``); f0 is RMVPE
-(``self.rmvpe``, loaded once from ``assets/models/predictors/rmvpe.pt`` or injected).
+``ContentVecAMD`` (``.pt`` embedder), ``net_g`` a ``SynthesizerAMD`` (``.pth``); the f0 estimators are the
+ones given to the constructor, or loaded once from their asset files on first use (f0.py's ``F0Bank``, which
+``VC`` shares with ``extract.FeatureInputAMD``).
 
 Everything runs on the device in the order of convert.py:388-458 -- the f64 filtfilt and
 reflect padding included (filtfilt.hip), and the quiet-point search for inputs > x_max (pipeline.hip;
@@ -18,8 +19,10 @@ FAISS retrieval (``file_index`` + ``index_rate``) runs on the device (retrieval.
 index file is read without faiss (faiss_index.py) and kept resident per path.
 
 f0 methods, all on the device: "rmvpe", "crepe-{tiny,small,medium,large,full}" (crepe.py), "pm" (pm.py),
-"swipe" (swipe.py) and "hybrid[a+b+...]" over those (f0mix.py: the members' raw tracks resampled and their
-nanmedian taken, as get_f0_hybrid).
+"swipe" (swipe.py), "fcpe" (fcpe.py), "fcpe-legacy" (fcpe_legacy.py; only while its model is at hand) and
+"hybrid[a+b+...]" over those (f0mix.py: the members' raw tracks resampled and their nanmedian taken, as
+get_f0_hybrid).  The list of names, the loaders and the members' raw tracks (``f0_raw``) are f0.py's; ``f0_device``
+here adds each method's own post step (shift, autotune, f0 file, mel quantiser).
 
 f0 autotune and f0 files run inside the f0 decode kernels; volume_envelope != 1 (change_rms) runs on
 the device after the segment loop.  Embedders: fairseq ``.pt`` and transformers ``.safetensors``
@@ -35,9 +38,9 @@ import numpy as np
 import torch
 from scipy import signal
 
-from . import _lib
 from . import contentvec as cvm
 from . import f0mix, ops
+from .f0 import F0Bank
 
 BH, AH = signal.butter(N=5, Wn=48, btype="high", fs=16000)  # convert.py:30
 
@@ -90,10 +93,7 @@ class Config:
         self.x_pad, self.x_query, self.x_center, self.x_max = (3, 10, 60, 65) if is_half else (1, 6, 38, 41)
 
 
-class VC:
-    CREPE_METHODS = {f"crepe-{c}": c for c in ("tiny", "small", "medium", "large", "full")}
-    HYBRID_EXTRA = ("fcpe",)  # hybrid members beyond f0mix.MEMBERS: the ones that need a model VC holds
-
+class VC(F0Bank):
     def __init__(self, tgt_sr, config, rmvpe=None, crepe=None, fcpe=None, fcpe_legacy=None):
         self.x_pad = config.x_pad
         self.x_query = config.x_query
@@ -110,14 +110,11 @@ class VC:
         self.f0_min, self.f0_max = 50, 1100
         self.device = config.device
         self.is_half = config.is_half
-        self.rmvpe = rmvpe
-        self.fcpe = fcpe  # FcpeAMD (loaded on first use otherwise)
-        self.fcpe_legacy = fcpe_legacy  # FcpeLegacyAMD (loaded on first use if its file is there, see _fcpe_legacy)
+        self._init_f0(rmvpe, crepe, fcpe, fcpe_legacy)  # the estimators given; the others load on first use (f0.py)
         # library-created streams (CU-masked) this VC owns: destroyed by close() / at exit, after their work
         self._owned = []
         self._finalizer = weakref.finalize(self, _close_streams, self._owned)
         self.embed_suffix = None  # pipeline()'s embed_suffix during that call (convert.py:390); None = the model's own
-        self.crepe = dict(crepe or {})  # capacity -> CrepeAMD (loaded on first use otherwise)
         # parity hook: noise_fn(seg, kind, shape) -> device tensor; kind "z" | "sine", and for the MRF-HiFi-GAN and
         # RefineGAN decoders also "phase" (the source's initial phases, uniform) and "adain<k>" (_decoder_noise)
         self.noise_fn = None
@@ -140,57 +137,22 @@ class VC:
                 opt_ts.append(t - self.t_query + np.where(seg == seg.min())[0][0])
         return opt_ts
 
-    def _rmvpe(self):
-        if self.rmvpe is None:
-            from .rmvpe import RMVPEAMD
-            self.rmvpe = RMVPEAMD.from_file(os.path.join("assets", "models", "predictors", "rmvpe.pt"), self.device)
-        return self.rmvpe
-
-    def _fcpe(self):
-        if self.fcpe is None:
-            from .fcpe import FcpeAMD
-            self.fcpe = FcpeAMD.from_file(os.path.join("assets", "models", "predictors", "fcpe.pt"), self.device)
-        return self.fcpe
-
-    FCPE_LEGACY_PT = os.path.join("assets", "models", "predictors", "fcpe_legacy.pt")
-
-    def _fcpe_legacy(self, required=True):
-        """The FcpeLegacyAMD this VC holds: the one it was given, or FCPE_LEGACY_PT loaded on first use.  Without
-        either "fcpe-legacy" is off the device path: None, or NotImplementedError when ``required``."""
-        if self.fcpe_legacy is None and os.path.exists(self.FCPE_LEGACY_PT):
-            from .fcpe_legacy import FcpeLegacyAMD
-            self.fcpe_legacy = FcpeLegacyAMD.from_file(self.FCPE_LEGACY_PT, self.device)
-        if self.fcpe_legacy is None and required:
-            raise NotImplementedError(f"f0 method 'fcpe-legacy' needs its model: pass fcpe_legacy=FcpeLegacyAMD(...) "
-                                      f"or provide {self.FCPE_LEGACY_PT}")
-        return self.fcpe_legacy
-
-    def _hybrid_extra(self, f0_method=""):
-        """The hybrid members beyond f0mix.MEMBERS: "fcpe-legacy" only while its model is at hand (a hybrid that
-        names it without one raises here, saying how to supply the model)."""
-        if self._fcpe_legacy(required=False) is not None:
-            return self.HYBRID_EXTRA + ("fcpe-legacy",)
-        if "fcpe-legacy" in [m.strip() for m in f0_method.partition("[")[2].partition("]")[0].split("+")]:
-            self._fcpe_legacy()
-        return self.HYBRID_EXTRA
-
-    def _crepe(self, capacity):
-        if capacity not in self.crepe:
-            from .crepe import CrepeAMD
-            self.crepe[capacity] = CrepeAMD.from_file(
-                os.path.join("assets", "models", "predictors", f"crepe_{capacity}.pth"), capacity, self.device)
-        return self.crepe[capacity]
-
     def f0_device(self, xp, pitch, f0_method="rmvpe", f0_autotune=False, f0_autotune_strength=1.0, inp_f0=None,
                   xp64=None, hop_length=64):
         """VC.get_f0 (convert.py:304-323) on the device: (coarse int64 [T], pitchf f32 [T]).  Autotune
         and the f0-file override run inside the decode kernels, in the reference's order.  "pm" reads the
         f64 signal ``xp64`` (the reference hands parselmouth the f64 filtfilt output); ``hop_length`` is the one
-        ``pipeline`` receives, which only "fcpe" and "fcpe-legacy" (alone or as hybrid members) read."""
+        ``pipeline`` receives, which only "fcpe" and "fcpe-legacy" (alone or as hybrid members) read.
+
+        rmvpe, crepe-* and swipe end in post kernels of their own (rvc_rmvpe_decode in f64, rvc_crepe_smooth_coarse
+        and rvc_swipe_post in f32, as NumPy promotes in the reference); pm, fcpe, fcpe-legacy and the hybrids end in
+        the f64 ops.f0_post64."""
+        self.check_f0_method(f0_method)  # raises for what is not on the device path, before any device work
         post = None
         if f0_autotune or inp_f0 is not None:
             rep, off = f0_override(inp_f0, self.x_pad) if inp_f0 is not None else (None, 0)
             post = ops.F0Post(f0_autotune_strength if f0_autotune else None, rep, off, xp.device)
+        p_len = xp.numel() // self.window
         if f0_method == "rmvpe":
             coarse, pitchf, _ = self._rmvpe().f0_device(xp, 0.03, float(pitch), post=post)
             return coarse, pitchf
@@ -199,75 +161,19 @@ class VC:
         if f0_method == "pm":
             if xp64 is None:
                 raise ValueError("f0 method 'pm' reads the f64 filtered signal (xp64)")
-            if getattr(self, "pm", None) is None:
-                from .pm import PitchPM
-                self.pm = PitchPM(xp64.device)
-            return self.pm.f0_device(xp64, xp.numel() // self.window, float(pitch), post=post)
+            return self._pm().f0_device(xp64, p_len, float(pitch), post=post)
         if f0_method == "swipe":
             # get_f0_swipe reads x.astype(np.float32) of the f64 filtered signal: xp is that rounding already
             # (filtfilt.hip's filt_reflect_pad stores (float)v beside the f64 v)
             return self._swipe(xp.device).f0_device(xp.contiguous(), float(pitch), post=post)
-        if f0_method == "fcpe":
-            # get_f0_fcpe (convert.py:239-246): the reference truncates f0_min / f0_max and the hop length
-            return self._fcpe().f0_device(xp.contiguous(), float(pitch), xp.numel() // self.window, post=post,
-                                          hop_length=int(hop_length), f0_min=int(self.f0_min),
-                                          f0_max=int(self.f0_max))
-        if f0_method == "fcpe-legacy":
-            # get_f0_fcpe(legacy=True): threshold 0.03; FCPE_LEGACY never reads f0_min / f0_max
-            return self._fcpe_legacy().f0_device(xp.contiguous(), float(pitch), xp.numel() // self.window, post=post,
-                                                 hop_length=int(hop_length))
         if f0mix.is_hybrid(f0_method):
-            members = f0mix.parse_hybrid(f0_method, extra=self._hybrid_extra(f0_method))
-            return self._f0_hybrid(xp, float(pitch), members, post, hop_length)
-        raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe, fcpe, fcpe-legacy (with its "
-                                  "model) and hybrid[...] over them are on the MI355X path")
-
-    def _swipe(self, device):
-        if getattr(self, "swipe", None) is None:
-            from .swipe import SwipeAMD
-            self.swipe = SwipeAMD(device)
-        return self.swipe
-
-    def f0_raw(self, x32, member, p_len, hop_length=64):
-        """One estimator's raw track (before any shift / autotune) on the device f32 signal x32, as
-        get_f0_hybrid's members return it: rmvpe f64 [1 + N//160], crepe-* f32 [1 + N//160], pm f64 padded to
-        p_len, swipe f32 [1 + N//160], fcpe and fcpe-legacy f64 [p_len]."""
-        if member == "rmvpe":
-            return self._rmvpe().f0_device(x32, 0.03, 0.0, want_f0=True)[2]
-        if member in self.CREPE_METHODS:
-            # shift 2^0 = 1 and no post: pitchf is the raw f0
-            return self._crepe(self.CREPE_METHODS[member]).f0_device(x32, 0.0)[1]
-        if member == "pm":
-            if getattr(self, "pm", None) is None:
-                from .pm import PitchPM
-                self.pm = PitchPM(x32.device)
-            f0 = self.pm.to_pitch_ac(x32.double())
-            pad = (p_len - f0.numel() + 1) // 2  # get_f0_pm's padding (convert.py:210-212)
-            if pad > 0 or p_len - f0.numel() - pad > 0:
-                f0 = torch.nn.functional.pad(f0, (pad, p_len - f0.numel() - pad))
-            return f0
-        if member == "swipe":
-            return self._swipe(x32.device).f0(x32)
-        if member == "fcpe":
-            return self._fcpe().f0(x32, p_len, int(hop_length), 0.006, int(self.f0_min), int(self.f0_max))
-        if member == "fcpe-legacy":
-            return self._fcpe_legacy().f0(x32, p_len, int(hop_length), 0.03)
-        raise NotImplementedError(f"hybrid f0 member {member!r}: rmvpe, crepe-*, pm, swipe, fcpe and fcpe-legacy "
-                                  "(with its model) are on the MI355X path")
-
-    def _f0_hybrid(self, xp, pitch, members, post, hop_length=64):
-        """get_f0_hybrid + get_f0's post (convert.py:283-323): every member reads the f32 signal divided by its
-        0.999 |x| quantile; the raw tracks are resampled to p_len and their nanmedian taken, in f64."""
-        from . import pm as _pm
-        p_len = xp.numel() // self.window
-        xn = f0mix.normalize(xp.contiguous())
-        f0 = f0mix.mix([self.f0_raw(xn, m, p_len, hop_length) for m in members], p_len)
-        coarse = torch.empty(p_len, dtype=torch.int64, device=xp.device)
-        pitchf = torch.empty(p_len, device=xp.device)
-        ops.check(_lib.load().rvc_pm_post(_pm._p64(f0), p_len, p_len, float(2.0 ** (pitch / 12)),
-                                          ops._post_ref(post, p_len), ops._p(coarse), ops._p(pitchf), ops._stream()),
-                  "pm_post")
-        return coarse, pitchf
+            # get_f0_hybrid (convert.py:283-302): every member reads the f32 signal divided by its 0.999 |x| quantile;
+            # the raw tracks are resampled to p_len and their nanmedian taken, in f64
+            xn = f0mix.normalize(xp.contiguous())
+            f0 = f0mix.mix([self.f0_raw(xn, m, p_len, hop_length) for m in self.f0_members(f0_method)], p_len)
+        else:  # "fcpe" / "fcpe-legacy": the raw track of get_f0_fcpe on the signal as it is
+            f0 = self.f0_raw(xp.contiguous(), f0_method, p_len, hop_length)
+        return ops.f0_post64(f0, p_len, float(pitch), post)
 
     # ------------------------------------------------------------------ device pieces
     def features_device(self, model, a0, version):
@@ -762,14 +668,7 @@ class VC:
                  suffix, embed_suffix, f0_file=None, f0_onnx=False, pbar=None):
         if f0_onnx:
             raise NotImplementedError("f0_onnx: ONNX f0 models are not on the MI355X path")
-        if f0mix.is_hybrid(f0_method):
-            # raises, naming the member, for one that is not on the device path
-            f0mix.parse_hybrid(f0_method, extra=self._hybrid_extra(f0_method))
-        elif f0_method == "fcpe-legacy":
-            self._fcpe_legacy()  # raises, saying how to supply the model, when there is none
-        elif f0_method not in ("rmvpe", "pm", "swipe", "fcpe") and f0_method not in self.CREPE_METHODS:
-            raise NotImplementedError(f"f0 method {f0_method!r}: rmvpe, crepe-*, pm, swipe, fcpe, fcpe-legacy (with "
-                                      "its model) and hybrid[...] over them are on the MI355X path")
+        self.check_f0_method(f0_method)  # raises, naming it, for a method or member that is not on the device path
         index = None
         if file_index != "" and os.path.exists(file_index) and index_rate != 0:  # convert.py:392-399
             index = self._index(file_index)

@@ -15,15 +15,11 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .ops import _p, _pd
 
 NW = 958  # Praat's nsamp_window for a 50 Hz floor at 16 kHz (3 periods, halved-and-doubled)
 BIX = NW // 2
-
-
-def _p64(t):
-    if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
-        raise TypeError(f"rvc_amd pm: expected a contiguous CUDA f64 tensor, got {t.dtype} on {t.device}")
-    return ctypes.c_void_p(t.data_ptr())
+_p64 = _pd  # the f64 pointer check under the name tests/test_gpu_f0mix.py reaches it by: ops' helper, not a copy
 
 
 class PitchPM:
@@ -47,18 +43,10 @@ class PitchPM:
         need = lib.rvc_pm_work_bytes(n)
         work = ops._workspace(x64.device, need, "pm")
         f0 = torch.empty(nf, dtype=torch.float64, device=x64.device)
-        ops.check(lib.rvc_pm_f0(_p64(x64.contiguous()), n, _p64(self.window), _p64(self.window_r), ops._p(work),
-                                need, _p64(f0), ops._stream()), "pm_f0")
+        ops.check(lib.rvc_pm_f0(_pd(x64.contiguous()), n, _pd(self.window), _pd(self.window_r), _p(work),
+                                need, _pd(f0), ops._stream()), "pm_f0")
         return f0
 
     def f0_device(self, x64: torch.Tensor, p_len: int, pitch_shift: float = 0.0, post=None):
         """get_f0(..., "pm") on the device: (coarse int64 [max(p_len, nf)], pitchf f32 [same])."""
-        f0 = self.to_pitch_ac(x64)
-        nf = f0.numel()
-        nout = max(p_len, nf)
-        coarse = torch.empty(nout, dtype=torch.int64, device=x64.device)
-        pitchf = torch.empty(nout, device=x64.device)
-        ops.check(_lib.load().rvc_pm_post(_p64(f0), nf, p_len, float(2.0 ** (pitch_shift / 12)),
-                                          ops._post_ref(post, nout), ops._p(coarse), ops._p(pitchf), ops._stream()),
-                  "pm_post")
-        return coarse, pitchf
+        return ops.f0_post64(self.to_pitch_ac(x64), p_len, pitch_shift, post)

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .ops import _p, _pd
 
 NC = 429  # pitch candidates
 (T_PC, T_FERBS, T_IDX, T_MU, T_W, T_K, T_WIN, T_TW, T_CMAP, T_CMU, T_PX, T_GRIDX, T_GRIDF0, T_WP, T_KP) = range(15)
@@ -24,10 +25,6 @@ def _p32(t, what="signal"):
     if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1:
         raise TypeError(f"rvc_amd swipe: expected a contiguous 1-D CUDA f32 {what}, got {t.dtype} "
                         f"{tuple(t.shape)} on {t.device}")
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _pv(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
@@ -66,7 +63,7 @@ class SwipeAMD:
             raise ValueError(f"swipe: bad signal length {n}")
         work = ops._workspace(x32.device, need, "swipe")
         S = torch.empty(NC, lib.rvc_swipe_frames(n), dtype=torch.float64, device=x32.device)
-        ops.check(lib.rvc_swipe_strength(xp, n, _pv(self.tables), _pv(work), need, _pv(S), ops._stream()),
+        ops.check(lib.rvc_swipe_strength(xp, n, _p(self.tables), _p(work), need, _pd(S), ops._stream()),
                   "swipe_strength")
         return S
 
@@ -77,7 +74,7 @@ class SwipeAMD:
                             f"{tuple(S.shape)} on {S.device}")
         F = S.shape[1]
         f0 = torch.empty(F, dtype=torch.float32, device=S.device)
-        ops.check(_lib.load().rvc_swipe_pick(_pv(S), F, _pv(self.tables), _pv(f0), ops._stream()), "swipe_pick")
+        ops.check(_lib.load().rvc_swipe_pick(_pd(S), F, _p(self.tables), _p(f0), ops._stream()), "swipe_pick")
         return f0
 
     def f0(self, x32: torch.Tensor) -> torch.Tensor:
@@ -90,6 +87,6 @@ class SwipeAMD:
         F = f0.numel()
         coarse = torch.empty(F, dtype=torch.int64, device=f0.device)
         pitchf = torch.empty(F, dtype=torch.float32, device=f0.device)
-        ops.check(_lib.load().rvc_swipe_post(_pv(f0), F, float(2.0 ** (pitch_shift / 12)), ops._post_ref(post, F),
-                                             _pv(coarse), _pv(pitchf), ops._stream()), "swipe_post")
+        ops.check(_lib.load().rvc_swipe_post(_p(f0), F, float(2.0 ** (pitch_shift / 12)), ops._post_ref(post, F),
+                                             _p(coarse), _p(pitchf), ops._stream()), "swipe_post")
         return coarse, pitchf

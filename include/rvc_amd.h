@@ -768,6 +768,35 @@ int rvc_kmeans_update(const float* x, int64_t n, int64_t d, const int64_t* list_
                       const float* cent_prev, float* cent_out, rvc_stream_t stream);
 int rvc_gather_rows(const float* x, int64_t d, const int64_t* ids, int64_t m, float* out, rvc_stream_t stream);
 
+/* The MiniBatchKMeans reduction of create_index.py:63-76 (sklearn 1.7.2, dense, unit sample weights), one mini-batch
+ * step at a time (minibatch.hip); the same contract as above.  xb [n][d] is the batch (rvc_gather_rows of x by the
+ * batch's row numbers), cent [k][d], weight_sums f32 [k] sklearn's _counts.  The RandomState, the loop, the choice of
+ * the centres to reassign and the stopping rule are host control (rvc_amd/index_train.py).
+ *
+ * rvc_minibatch_assign: rvc_kmeans_assign with k > n allowed (a batch is smaller than the 10000 centres); the same
+ *   kernels, workspace (rvc_kmeans_assign_work_bytes) and results.
+ * rvc_minibatch_update: _minibatch_update_dense over the CSR lists rvc_kmeans_lists makes of the batch's assignment.
+ *   Per centre with members: row = cent_prev * weight (an f32 product rounded on its own, no fma with the first add),
+ *   row += x for the members in batch order, weight += members, row *= 1.f / weight; a centre with no member is copied.
+ *   sklearn's arithmetic bit for bit.  weight_sums is updated in place; cent_out != cent_prev.
+ * rvc_minibatch_inertia: sum_i ||xb_i - cent[assign_i]||^2 with differences and squares in f64 from the f32 operands,
+ *   added in a fixed order (two stages, no atomics) into status->inertia.  The same block receives what the host needs
+ *   once per step from weight_sums as it is when this runs: wmax (the largest weight) and any_zero (1 if a weight is
+ *   0); weight_sums NULL leaves them 0.  assign values outside [0, k) are clamped.  status: 32 bytes, 8-byte aligned
+ *   { double inertia; float wmax; int32_t any_zero; int64_t reserved[2]; }.  work: rvc_minibatch_inertia_work_bytes(n).
+ * rvc_minibatch_scatter: the reassignment: cent[dst[i]] = xb[src[i]] and weight_sums[dst[i]] = v for i < m; the dst
+ *   are distinct (the caller guarantees it), src may repeat; a dst outside [0, k) is skipped, src is clamped. */
+int rvc_minibatch_assign(const float* x, int64_t n, int64_t d, const float* cent, int64_t k, void* work,
+                         int64_t work_bytes, int32_t* assign, float* dist, rvc_stream_t stream);
+int rvc_minibatch_update(const float* xb, int64_t n, int64_t d, const int64_t* list_off, const int64_t* ids, int64_t k,
+                         const float* cent_prev, float* weight_sums, float* cent_out, rvc_stream_t stream);
+int64_t rvc_minibatch_status_bytes(void);
+int64_t rvc_minibatch_inertia_work_bytes(int64_t n);
+int rvc_minibatch_inertia(const float* xb, int64_t n, int64_t d, const float* cent, int64_t k, const int32_t* assign,
+                          const float* weight_sums, void* work, int64_t work_bytes, void* status, rvc_stream_t stream);
+int rvc_minibatch_scatter(const float* xb, int64_t n, int64_t d, const int64_t* src, const int64_t* dst, int64_t m,
+                          float v, float* cent, int64_t k, float* weight_sums, rvc_stream_t stream);
+
 /* ------------------------------------------------------------------ CREPE f0 (VC.get_f0_crepe, convert.py:230-237)
  * crepe_frames: CREPE.py:151-171 framing (1024 @ hop, 512 zero pad) + per-frame zero-mean / unbiased-std
  *   normalisation of frames [frame0, frame0 + nframes) -> out [nframes][1024].

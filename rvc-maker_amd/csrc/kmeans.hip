@@ -1,6 +1,7 @@
 // IVF training on the device: the k-means of faiss's IndexIVFFlat::train (Clustering::train with niter = 10, as
 // create_index.py:66-83 reaches it through index_factory("IVF{n},Flat").train) and the list assignment of add.
 // Host control (initial permutation, split of empty clusters, the iteration loop) is rvc_amd/index_train.py.
+// rvc_minibatch_assign (the MiniBatchKMeans reduction, minibatch.hip) is the same assignment with k > n allowed.
 //
 //   kmeans_prep_kernel      ||c_j||^2 and ||x_i||^2 in f32 (one wave per row), and the (value, index) cells reset
 //   kmeans_assign_kernel    block = 128 rows x a run of 128-centroid tiles; <c_j, x_i> on v_mfma_f32_32x32x2_f32 (exact
@@ -369,15 +370,11 @@ extern "C" int64_t rvc_kmeans_assign_work_bytes(int64_t n, int64_t d, int64_t k)
     return n * 8 + ((n + 3) / 4 * 4 + (k + 3) / 4 * 4) * 4;  // cells u64 [n], xnorm f32 [n], cnorm f32 [k]
 }
 
-extern "C" int rvc_kmeans_assign(const float* x, int64_t n, int64_t d, const float* cent, int64_t k, void* work,
-                                 int64_t work_bytes, int32_t* assign, float* dist, rvc_stream_t stream) {
-    RVC_CHECK_ARG(x && cent && work && assign && dist, "kmeans_assign: null pointer");
-    RVC_CHECK_ARG(dim_ok(d), "kmeans_assign: d=%lld must be a multiple of 8 in [8, 1024]", (long long)d);
-    RVC_CHECK_ARG(k >= 1 && n >= k && n <= NMAX, "kmeans_assign: bad sizes n=%lld k=%lld (1 <= k <= n)", (long long)n,
-                  (long long)k);
-    RVC_CHECK_ARG(work_bytes >= rvc_kmeans_assign_work_bytes(n, d, k), "kmeans_assign: workspace too small");
-    RVC_CHECK_ARG(aligned16(x) && aligned16(cent) && aligned16(work), "kmeans_assign: x, cent, work 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
+// The launches of an assignment whose arguments have been validated.  Nothing in them needs k <= n: rows past n and
+// centroids past k are clamped reads whose results are dropped (cnorm = +inf), and the centroid axis is split over
+// grid.y whenever the rows alone do not fill the device.
+static int assign_launch(const float* x, int64_t n, int64_t d, const float* cent, int64_t k, void* work, int32_t* assign,
+                         float* dist, hipStream_t s) {
     u64* best = (u64*)work;
     float* xnorm = (float*)(best + n);
     float* cnorm = xnorm + (n + 3) / 4 * 4;
@@ -400,6 +397,29 @@ extern "C" int rvc_kmeans_assign(const float* x, int64_t n, int64_t d, const flo
                        (const float*)xnorm, (int)n, (int)k, assign, dist);
     RVC_HIP(hipGetLastError());
     return RVC_OK;
+}
+
+extern "C" int rvc_kmeans_assign(const float* x, int64_t n, int64_t d, const float* cent, int64_t k, void* work,
+                                 int64_t work_bytes, int32_t* assign, float* dist, rvc_stream_t stream) {
+    RVC_CHECK_ARG(x && cent && work && assign && dist, "kmeans_assign: null pointer");
+    RVC_CHECK_ARG(dim_ok(d), "kmeans_assign: d=%lld must be a multiple of 8 in [8, 1024]", (long long)d);
+    RVC_CHECK_ARG(k >= 1 && n >= k && n <= NMAX, "kmeans_assign: bad sizes n=%lld k=%lld (1 <= k <= n)", (long long)n,
+                  (long long)k);
+    RVC_CHECK_ARG(work_bytes >= rvc_kmeans_assign_work_bytes(n, d, k), "kmeans_assign: workspace too small");
+    RVC_CHECK_ARG(aligned16(x) && aligned16(cent) && aligned16(work), "kmeans_assign: x, cent, work 16-byte aligned");
+    return assign_launch(x, n, d, cent, k, work, assign, dist, (hipStream_t)stream);
+}
+
+// The same assignment for a mini-batch: k may exceed n (2048 rows against 10000 centres).
+extern "C" int rvc_minibatch_assign(const float* x, int64_t n, int64_t d, const float* cent, int64_t k, void* work,
+                                    int64_t work_bytes, int32_t* assign, float* dist, rvc_stream_t stream) {
+    RVC_CHECK_ARG(x && cent && work && assign && dist, "minibatch_assign: null pointer");
+    RVC_CHECK_ARG(dim_ok(d), "minibatch_assign: d=%lld must be a multiple of 8 in [8, 1024]", (long long)d);
+    RVC_CHECK_ARG(k >= 1 && n >= 1 && n <= NMAX && k <= NMAX, "minibatch_assign: bad sizes n=%lld k=%lld", (long long)n,
+                  (long long)k);
+    RVC_CHECK_ARG(work_bytes >= rvc_kmeans_assign_work_bytes(n, d, k), "minibatch_assign: workspace too small");
+    RVC_CHECK_ARG(aligned16(x) && aligned16(cent) && aligned16(work), "minibatch_assign: x, cent, work 16-byte aligned");
+    return assign_launch(x, n, d, cent, k, work, assign, dist, (hipStream_t)stream);
 }
 
 extern "C" int64_t rvc_kmeans_lists_work_bytes(int64_t n, int64_t k) {

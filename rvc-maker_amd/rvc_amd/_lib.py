@@ -271,6 +271,16 @@ SIGNATURES = {
     "rvc_kmeans_lists": [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
     "rvc_kmeans_update": [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     "rvc_gather_rows": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
+    "rvc_minibatch_assign": [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                             c_void_p],
+    "rvc_minibatch_update": [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                             c_void_p],
+    "rvc_minibatch_status_bytes": [],
+    "rvc_minibatch_inertia_work_bytes": [c_int64],
+    "rvc_minibatch_inertia": [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                              c_void_p, c_void_p],
+    "rvc_minibatch_scatter": [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int64,
+                              c_void_p, c_void_p],
     "rvc_crepe_frames": [c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p],
     "rvc_bn_maxpool": [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
                        c_void_p],
@@ -344,6 +354,7 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_swipe_tables_bytes": c_int64, "rvc_swipe_table_dims": c_int64,
              "rvc_abs_quantile_work_bytes": c_int64, "rvc_formant_work_bytes": c_int64,
              "rvc_kmeans_assign_work_bytes": c_int64, "rvc_kmeans_lists_work_bytes": c_int64,
+             "rvc_minibatch_status_bytes": c_int64, "rvc_minibatch_inertia_work_bytes": c_int64,
              "rvc_groupnorm_work_bytes": c_int64, "rvc_fcpe_post_work_bytes": c_int64,
              "rvc_performer_work_bytes": c_int64,
              "rvc_lfilter64_warmup": c_int64, "rvc_lfilter64_work_bytes": c_int64, "rvc_frame_rms64_len": c_int64}

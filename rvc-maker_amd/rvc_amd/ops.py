@@ -9,6 +9,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1133,6 +1134,90 @@ def gather_rows(x, ids):
     out = torch.empty(ids.numel(), d, dtype=torch.float32, device=x.device)
     check(_lib.load().rvc_gather_rows(_p(x), d, _p(ids), ids.numel(), _p(out), _stream()), "gather_rows")
     return out
+
+
+def minibatch_assign(x, cent, assign=None, dist=None):
+    """kmeans_assign for a mini-batch: k may exceed n (kmeans.hip, the same kernels)."""
+    (n, d), (k, dc) = _rows(x, "minibatch_assign"), _rows(cent, "minibatch_assign")
+    if dc != d:
+        raise ValueError(f"minibatch_assign: centroid dim {dc} != {d}")
+    assign = torch.empty(n, dtype=torch.int32, device=x.device) if assign is None else assign
+    dist = torch.empty(n, dtype=torch.float32, device=x.device) if dist is None else dist
+    if assign.numel() < n or dist.numel() < n or assign.dtype != torch.int32:
+        raise ValueError("minibatch_assign: output buffers too small")
+    lib = _lib.load()
+    need = lib.rvc_kmeans_assign_work_bytes(n, d, k)
+    if need < 0:
+        raise ValueError(f"minibatch_assign: bad sizes n={n} d={d} k={k}")
+    ws = _workspace(x.device, need, "kmeans")
+    check(lib.rvc_minibatch_assign(_p(x), n, d, _p(cent), k, _p(ws), need, _p(assign), _p(dist), _stream()),
+          "minibatch_assign")
+    return assign, dist
+
+
+def _weights(w, k, what):
+    if w.dim() != 1 or w.dtype != torch.float32 or not w.is_contiguous() or not w.is_cuda or w.numel() != k:
+        raise TypeError(f"{what}: weight_sums must be a contiguous CUDA f32 [{k}] tensor")
+
+
+def minibatch_update(xb, list_off, ids, cent_prev, weight_sums, out=None):
+    """sklearn's _minibatch_update_dense over the batch's CSR lists (minibatch.hip): new centres [k][d];
+    weight_sums f32 [k] is updated in place."""
+    (n, d), (k, dc) = _rows(xb, "minibatch_update"), _rows(cent_prev, "minibatch_update")
+    if dc != d or list_off.numel() < k + 1 or ids.numel() < n or list_off.dtype != torch.int64 or \
+            ids.dtype != torch.int64:
+        raise ValueError("minibatch_update: size mismatch")
+    _weights(weight_sums, k, "minibatch_update")
+    out = torch.empty_like(cent_prev) if out is None else out
+    if out.shape != cent_prev.shape or out.data_ptr() == cent_prev.data_ptr() or not out.is_contiguous():
+        raise ValueError("minibatch_update: out must be a separate [k][d] tensor")
+    check(_lib.load().rvc_minibatch_update(_p(xb), n, d, _p(list_off), _p(ids), k, _p(cent_prev), _p(weight_sums),
+                                           _p(out), _stream()), "minibatch_update")
+    return out
+
+
+MINIBATCH_STATUS = np.dtype([("inertia", "<f8"), ("wmax", "<f4"), ("any_zero", "<i4"), ("reserved", "<i8", (2,))])
+
+
+def minibatch_inertia(xb, cent, assign, weight_sums=None, status=None):
+    """sum_i ||xb_i - cent[assign_i]||^2 in f64 into the 32-byte device status block (uint8 [32], returned), with
+    the largest weight and whether a weight is 0; ``minibatch_status`` reads it on the host."""
+    (n, d), (k, dc) = _rows(xb, "minibatch_inertia"), _rows(cent, "minibatch_inertia")
+    if dc != d or assign.dim() != 1 or assign.dtype != torch.int32 or assign.numel() < n or \
+            not assign.is_contiguous():
+        raise ValueError("minibatch_inertia: size mismatch")
+    if weight_sums is not None:
+        _weights(weight_sums, k, "minibatch_inertia")
+    lib = _lib.load()
+    nbytes = lib.rvc_minibatch_status_bytes()
+    status = torch.empty(nbytes, dtype=torch.uint8, device=xb.device) if status is None else status
+    if status.dtype != torch.uint8 or status.numel() < nbytes or not status.is_contiguous():
+        raise ValueError(f"minibatch_inertia: status must be a contiguous uint8 [{nbytes}] tensor")
+    need = lib.rvc_minibatch_inertia_work_bytes(n)
+    if need < 0:
+        raise ValueError(f"minibatch_inertia: bad size n={n}")
+    ws = _workspace(xb.device, need, "minibatch")
+    check(lib.rvc_minibatch_inertia(_p(xb), n, d, _p(cent), k, _p(assign), _p(weight_sums), _p(ws), need, _p(status),
+                                    _stream()), "minibatch_inertia")
+    return status
+
+
+def minibatch_status(status):
+    """The status block on the host (one synchronising read): (inertia, wmax, any_zero)."""
+    s = status.cpu().numpy()[:MINIBATCH_STATUS.itemsize].view(MINIBATCH_STATUS)[0]
+    return float(s["inertia"]), np.float32(s["wmax"]), bool(s["any_zero"])
+
+
+def minibatch_scatter(xb, src, dst, value, cent, weight_sums):
+    """cent[dst[i]] = xb[src[i]] and weight_sums[dst[i]] = value (int64 device src / dst, the dst distinct)."""
+    (n, d), (k, dc) = _rows(xb, "minibatch_scatter"), _rows(cent, "minibatch_scatter")
+    _weights(weight_sums, k, "minibatch_scatter")
+    if dc != d or src.dtype != torch.int64 or dst.dtype != torch.int64 or src.dim() != 1 or \
+            src.shape != dst.shape or not src.is_contiguous() or not dst.is_contiguous():
+        raise ValueError("minibatch_scatter: src and dst must be contiguous int64 [m] tensors")
+    check(_lib.load().rvc_minibatch_scatter(_p(xb), n, d, _p(src), _p(dst), src.numel(), float(value), _p(cent), k,
+                                            _p(weight_sums), _stream()), "minibatch_scatter")
+    return cent
 
 
 def phone_upsample(feats, feats0, pitchf, out, C, Tf, T, protect):

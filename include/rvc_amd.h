@@ -489,6 +489,13 @@ typedef struct rvc_f0_post {
 
 int rvc_rmvpe_decode(const float* sal, int64_t ld, int64_t F, double thred, double shift, const rvc_f0_post* post,
                      double* f0, int64_t* coarse, float* pitchf, rvc_stream_t stream);
+/* rmvpe-legacy (get_f0_rmvpe(legacy=True), convert.py:248-255; RMVPE.infer_from_audio_with_pitch, RMVPE.py:228-234):
+ * rvc_rmvpe_decode with f0[(f0 < f0_min) | (f0 > f0_max)] = 0 on the decoded f64 f0 (VC passes 50 and 1100; the bins
+ * span 31.7 .. 2005 Hz), in the same kernel, before the autotune / shift / f0 file of `post` and the quantiser.
+ * rvc_rmvpe_decode is this entry at (-inf, +inf), where the test is never true.  A NaN bound is RVC_EINVAL. */
+int rvc_rmvpe_decode_range(const float* sal, int64_t ld, int64_t F, double thred, double f0_min, double f0_max,
+                           double shift, const rvc_f0_post* post, double* f0, int64_t* coarse, float* pitchf,
+                           rvc_stream_t stream);
 
 /* pm f0 (VC.get_f0_pm, convert.py:206-213): Praat's To Pitch (ac) with get_f0_pm's settings on the f64
  * 16 kHz signal x [n] -> f0 [rvc_pm_frames(n)] (0 = unvoiced); window [958] = Praat's Hann window
@@ -550,10 +557,22 @@ int rvc_swipe_post(const float* f0, int64_t F, float shift, const rvc_f0_post* p
  *   rvc_abs_quantile  np.quantile(np.abs(x), 0.999) of f32 x [n] -> device f32 scalar q_out, as NumPy 2
  *                     evaluates it for an f32 array (index, gamma and lerp in f32); a radix select, no sort;
  *                     work: rvc_abs_quantile_work_bytes() bytes of device memory
+ *   rvc_abs_quantile_as  the same with the last step named: RVC_QUANTILE_NUMPY is rvc_abs_quantile;
+ *                     RVC_QUANTILE_TORCH is torch.quantile(torch.abs(x), 0.999) as ATen's CPU kernel evaluates it
+ *                     (FeatureInput.get_mangio_crepe, extract.py:166): the same f32 rank and order statistics, but
+ *                     each branch of the lerp is one fused multiply-add, which moves the last bit of about one
+ *                     result in a hundred
  *   rvc_div_scalar    out[i] = x[i] / q[0], a true f32 division by the device scalar (out may be x)
  *   rvc_f0_mix        M <= RVC_F0_MIX_MAX raw tracks (device f32 or f64, each with its own length) -> out f64
  *                     [p_len]: np.interp(np.linspace(0, n_m, p_len), np.arange(n_m), f0_m) in f64 per track,
  *                     then np.nanmedian over the tracks (one track: the resampled track).  p_len >= 2.
+ *   rvc_f0_resample_nan  the tail of get_f0_mangio_crepe (convert.py:226-228; the same expression ends get_f0_yin):
+ *                     source f32 [T] -> out f64 [p_len] in one launch: source[source < 0.001] = nan (an f32
+ *                     compare), np.interp(np.arange(0, T * p_len, T) / p_len, np.arange(T), source) in f64 by
+ *                     NumPy's rules (an exact hit returns fp[j]; a position past T - 1 returns fp[-1]; a NaN result
+ *                     is retried from the other end point, then takes the common value of two equal end points),
+ *                     then np.nan_to_num (nan -> 0, +-inf -> +-DBL_MAX).  T, p_len >= 1.  It shares rvc_f0_mix's
+ *                     np.interp device function.
  * The mixed track's autotune / shift / f0 file / quantiser is rvc_pm_post with nf = p_len. */
 enum { RVC_F0_MIX_MAX = 8 };
 typedef struct rvc_f0_track {
@@ -563,8 +582,12 @@ typedef struct rvc_f0_track {
 } rvc_f0_track;
 int64_t rvc_abs_quantile_work_bytes(void);
 int rvc_abs_quantile(const float* x, int64_t n, void* work, int64_t work_bytes, float* q_out, rvc_stream_t stream);
+enum { RVC_QUANTILE_NUMPY = 0, RVC_QUANTILE_TORCH = 1 };
+int rvc_abs_quantile_as(const float* x, int64_t n, int lerp, void* work, int64_t work_bytes, float* q_out,
+                        rvc_stream_t stream);
 int rvc_div_scalar(const float* x, int64_t n, const float* q, float* out, rvc_stream_t stream);
 int rvc_f0_mix(const rvc_f0_track* tracks, int M, int64_t p_len, double* out, rvc_stream_t stream);
+int rvc_f0_resample_nan(const float* source, int64_t T, int64_t p_len, double* out, rvc_stream_t stream);
 
 /* fcpe f0 (VC.get_f0_fcpe, convert.py:239-246: the conv-only CFNaiveMelPE of main/library/predictors/FCPE.py).
  * A host runs, per signal: rvc_fcpe_mel; rvc_conv1d (k=3, 128 -> C); rvc_groupnorm_act; rvc_conv1d (k=3);
@@ -804,7 +827,28 @@ int rvc_minibatch_scatter(const float* xb, int64_t n, int64_t d, const int64_t* 
  * crepe_decode: probs [360][T] sigmoid outputs (masked in place to -inf outside [lo, hi)), softmax,
  *   librosa Viterbi per sequence [seq_off[i], seq_off[i+1]) with log_trans[j][k] = log(A[k][j] + tiny),
  *   bins -> Hz with dither cents [T], periodicity -> f0_raw [T], pd_raw [T].
- * crepe_smooth_coarse: mean3(f0), median3(pd), f0[pd < 0.1] = 0, then get_f0's shift + coarse mel bins. */
+ * crepe_decode_as: crepe_decode with the power of two of bins -> Hz (10 * 2^((cents + dither) / 1200), f32) named:
+ *   RVC_CREPE_HZ_POWF is crepe_decode (the device's powf, within 1 ulp).  RVC_CREPE_HZ_TORCH restates, step for step
+ *   in f32 operations and fused multiply-adds, the VECTOR path of torch's CPU pow(2, y) on x86 hosts with FMA (a
+ *   1-ulp routine, not the correctly rounded value).  That is the reference's value for every frame torch sends
+ *   through whole vector blocks.  torch computes the tail of each call (each batch of 2 * hop_length frames here:
+ *   its last n mod 32 frames with 16-lane vectors, n mod 16 with 8-lane ones) with the C library's powf, which
+ *   differs in the last bit of about 2 % of values; on those frames, and on hosts without such a vector unit, the
+ *   two are 1 ulp apart there.  mangio-crepe-* uses this form: its track does not depend on a host.
+ * crepe_smooth_coarse: mean3(f0), median3(pd), f0[pd < 0.1] = 0, then get_f0's shift + coarse mel bins.
+ *
+ * mangio-crepe-<capacity> (VC.get_f0_mangio_crepe, convert.py:215-228) is the same network behind another framing and
+ * decode; it is the CREPE route that reads hop_length.  A host runs, on the f32 signal x [N]:
+ *   rvc_abs_quantile, rvc_div_scalar   x / np.quantile(|x|, 0.999) (inside a hybrid the signal was divided once
+ *                                      already and is divided again; the extraction twin, extract.py:162-171,
+ *                                      divides by torch.quantile: rvc_abs_quantile_as)
+ *   rvc_crepe_frames                   hop = hop_length, T = 1 + N / hop_length frames
+ *   the network                        as for crepe-<capacity>, in batches of any size (frames are independent)
+ *   rvc_crepe_decode_as (HZ_TORCH)     seq_off = 0, 2 hop, 4 hop, ..., T: predict(batch_size = 2 * hop_length)
+ *                                      restarts the Viterbi at every batch; dither [T] in frame order; pd_raw unused
+ *                                      (no periodicity gate, no mean / median)
+ *   rvc_f0_resample_nan                f0_raw [T] -> f64 [p_len]
+ *   rvc_pm_post (nf = p_len)           get_f0's autotune / shift / f0 file / quantiser in f64 */
 int rvc_crepe_frames(const float* audio, int64_t n, int hop, int64_t frame0, int64_t nframes, float* out,
                      rvc_stream_t stream);
 int rvc_bn_maxpool(const float* y, int64_t B, int64_t C, int64_t L, const float* alpha, const float* beta, float* out,
@@ -813,6 +857,10 @@ int64_t rvc_crepe_decode_ws_bytes(int64_t T);
 int rvc_crepe_decode(float* probs, int64_t T, int lo, int hi, const int64_t* seq_off, int nseq, const double* log_trans,
                      double log_off, double log_p_init, const float* dither, void* ws, int64_t ws_bytes, float* f0_raw,
                      float* pd_raw, rvc_stream_t stream);
+enum { RVC_CREPE_HZ_POWF = 0, RVC_CREPE_HZ_TORCH = 1 };
+int rvc_crepe_decode_as(float* probs, int64_t T, int lo, int hi, const int64_t* seq_off, int nseq,
+                        const double* log_trans, double log_off, double log_p_init, const float* dither, int hz,
+                        void* ws, int64_t ws_bytes, float* f0_raw, float* pd_raw, rvc_stream_t stream);
 int rvc_crepe_smooth_coarse(const float* f0_raw, const float* pd_raw, int64_t T, float shift, double mel_min,
                             double mel_max, const rvc_f0_post* post, int64_t* coarse, float* pitchf,
                             rvc_stream_t stream);
@@ -964,6 +1012,8 @@ int rvc_load_index(rvc_ctx* ctx, const rvc_ivf_index* index);
 /* device memory in use on the current device (hipMemGetInfo total - free), for load / reload accounting */
 int64_t rvc_device_bytes_in_use(void);
 
+/* The model-level rvc_vc_convert[_ex] keeps these three f0 methods: swipe, fcpe, fcpe-legacy, mangio-crepe-*,
+ * rmvpe-legacy and the hybrids are reached through the op-level entries above (and the Python VC). */
 enum { RVC_F0_RMVPE = 0, RVC_F0_CREPE = 1, RVC_F0_PM = 2 };
 typedef struct rvc_vc_opts {
     int f0_method;               /* RVC_F0_RMVPE (default), RVC_F0_CREPE (the model of rvc_load_crepe), RVC_F0_PM */

@@ -166,14 +166,56 @@ __global__ __launch_bounds__(384) void crepe_viterbi_kernel(const float* sm, int
     }
 }
 
-// bins -> Hz (CREPE.py:116-118) with dither cents, and periodicity = masked probability at the bin
+// 2^y in f32 as the VECTOR path of torch's CPU pow(2, y) evaluates it on x86 hosts with FMA (its vector math
+// library's 1-ulp powf; every step is an f32 operation or a fused multiply-add, so the device reproduces every
+// bit): y * log(2) as a two-float product, then exp of the two-float argument: reduce by q = rint(d / log 2) with a
+// split log 2, a degree-5 polynomial on the head, the square and the product in two-float arithmetic, 1 + t, scaled
+// by 2^q.  torch computes the tail of each call (what is left after whole vector blocks) with the C library's powf
+// instead: on those frames the reference itself is this value only where the two routines agree (about 98 %).
+// For the finite, moderate y of bins -> Hz (1.6 .. 7.7): no overflow, underflow or special-case handling.
+struct F2 {
+    float x, y;
+};
+RVC_DEV F2 f2_mul_f(F2 a, float b) {
+    const float rx = a.x * b;
+    return {rx, fmaf(a.y, b, fmaf(a.x, b, -rx))};
+}
+RVC_DEV F2 f2_add2_f(F2 a, float b) {
+    const float rx = a.x + b, v = rx - a.x;
+    return {rx, ((a.x - (rx - v)) + (b - v)) + a.y};
+}
+RVC_DEV float pow2_torch(float y) {
+    const F2 d = f2_mul_f({0.69314718246459960938f, -1.904654323148236017e-09f}, y);
+    const float q = rintf((d.x + d.y) * 1.442695040888963407359924681001892137426645954152985934135449406931f);
+    F2 s = f2_add2_f(d, q * -0.693145751953125f);
+    s = f2_add2_f(s, q * -1.428606765330187045e-06f);
+    const float nx = s.x + s.y;
+    s = {nx, s.x - nx + s.y};
+    float u = 0.00136324646882712841033936f;
+    u = fmaf(u, s.x, 0.00836596917361021041870117f);
+    u = fmaf(u, s.x, 0.0416710823774337768554688f);
+    u = fmaf(u, s.x, 0.166665524244308471679688f);
+    u = fmaf(u, s.x, 0.499999850988388061523438f);
+    const float qx = s.x * s.x;
+    const F2 m = f2_mul_f({qx, fmaf(s.x + s.x, s.y, fmaf(s.x, s.x, -qx))}, u);
+    const float tx = s.x + m.x;
+    const float ty = s.x - tx + m.x + s.y + m.y;
+    const float ox = 1.f + tx;
+    const float oy = 1.f - ox + tx + ty;
+    return ldexpf(ox + oy, (int)q);
+}
+
+// bins -> Hz (CREPE.py:116-118) with dither cents, and periodicity = masked probability at the bin.  TORCH_POW: the
+// power of two of torch's vector path (rvc_crepe_decode_as), else the device's powf (within 1 ulp of it).
+template <bool TORCH_POW>
 __global__ __launch_bounds__(256) void crepe_freq_kernel(const int64_t* states, const float* dither, const float* p,
                                                          int64_t T, float* f0, float* pd) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= T) return;
     const int64_t b = states[t];
     const float cents = (float)(20 * b) + 1997.3794084376191f;
-    f0[t] = 10.f * powf(2.f, (cents + dither[t]) / 1200.f);
+    const float e = (cents + dither[t]) / 1200.f;
+    f0[t] = 10.f * (TORCH_POW ? pow2_torch(e) : powf(2.f, e));
     pd[t] = p[b * T + t];
 }
 
@@ -228,6 +270,15 @@ extern "C" int rvc_bn_maxpool(const float* y, int64_t B, int64_t C, int64_t L, c
 extern "C" int rvc_crepe_decode(float* probs, int64_t T, int lo, int hi, const int64_t* seq_off, int nseq,
                                 const double* log_trans, double log_off, double log_p_init, const float* dither,
                                 void* ws, int64_t ws_bytes, float* f0_raw, float* pd_raw, rvc_stream_t stream) {
+    return rvc_crepe_decode_as(probs, T, lo, hi, seq_off, nseq, log_trans, log_off, log_p_init, dither,
+                               RVC_CREPE_HZ_POWF, ws, ws_bytes, f0_raw, pd_raw, stream);
+}
+
+extern "C" int rvc_crepe_decode_as(float* probs, int64_t T, int lo, int hi, const int64_t* seq_off, int nseq,
+                                   const double* log_trans, double log_off, double log_p_init, const float* dither,
+                                   int hz, void* ws, int64_t ws_bytes, float* f0_raw, float* pd_raw,
+                                   rvc_stream_t stream) {
+    RVC_CHECK_ARG(hz == RVC_CREPE_HZ_POWF || hz == RVC_CREPE_HZ_TORCH, "crepe_decode: unknown bins -> Hz form %d", hz);
     RVC_CHECK_ARG(probs && seq_off && log_trans && dither && ws && f0_raw && pd_raw && T > 0 && nseq > 0 &&
                       0 <= lo && lo <= hi && hi <= NB, "crepe_decode: bad args");
     const int64_t need = T * NB * 4 + T * NB * 2 + T * 8;
@@ -239,8 +290,12 @@ extern "C" int rvc_crepe_decode(float* probs, int64_t T, int lo, int hi, const i
     hipLaunchKernelGGL(crepe_softmax_kernel, dim3((unsigned)T), dim3(64), 0, s, probs, T, lo, hi, sm);
     hipLaunchKernelGGL(crepe_viterbi_kernel, dim3((unsigned)nseq), dim3(384), 0, s, sm, T, seq_off, log_trans, log_off,
                        log_p_init, ptr, states);
-    hipLaunchKernelGGL(crepe_freq_kernel, dim3(cdiv(T, 256)), dim3(256), 0, s, states, dither, probs, T, f0_raw,
-                       pd_raw);
+    if (hz == RVC_CREPE_HZ_TORCH)
+        hipLaunchKernelGGL(crepe_freq_kernel<true>, dim3(cdiv(T, 256)), dim3(256), 0, s, states, dither, probs, T,
+                           f0_raw, pd_raw);
+    else
+        hipLaunchKernelGGL(crepe_freq_kernel<false>, dim3(cdiv(T, 256)), dim3(256), 0, s, states, dither, probs, T,
+                           f0_raw, pd_raw);
     RVC_HIP(hipGetLastError());
     return RVC_OK;
 }

@@ -10,6 +10,8 @@
 //   div_scalar     x / q element-wise, a true f32 division by the device scalar
 //   f0_mix         per output frame: np.interp(np.linspace(0, n_m, p_len)[k], np.arange(n_m), f0_m) in f64 for
 //                  every track, then np.nanmedian over the tracks (the resampled track itself for one)
+//   f0_resample_nan  get_f0_mangio_crepe's tail (convert.py:226-228): values below 0.001 -> NaN, np.interp onto
+//                  p_len frames (the same np.interp device function as f0_mix), np.nan_to_num
 // The f64 post (autotune / shift / f0 file / quantiser) of the mixed track is rvc_pm_post with nf = p_len.
 #include "rvc_common.h"
 #include <algorithm>
@@ -137,7 +139,7 @@ __global__ __launch_bounds__(QT) void q_succ_kernel(const float* x, int64_t n, Q
     if (tid == 0 && scan[0] != 0xffffffffu) atomicMax(&w->succ_inv, ~scan[0]);
 }
 
-__global__ __launch_bounds__(QT) void q_final_kernel(int64_t n, QWork* w, float* out) {
+__global__ __launch_bounds__(QT) void q_final_kernel(int64_t n, QWork* w, int fused, float* out) {
 #pragma clang fp contract(off)
     __shared__ unsigned scan[QT];
     __shared__ unsigned res[3];
@@ -153,6 +155,8 @@ __global__ __launch_bounds__(QT) void q_final_kernel(int64_t n, QWork* w, float*
     const float diff = b - a;
     float r = a + diff * gamma;
     if (gamma >= 0.5f) r = b - diff * (1.f - gamma);
+    // torch.quantile's lerp (ATen's CPU lerp): the same two branches, each one fused multiply-add
+    if (fused) r = gamma < 0.5f ? fmaf(gamma, diff, a) : fmaf(gamma - 1.f, diff, b);
     out[0] = r;
 }
 
@@ -163,6 +167,27 @@ __global__ __launch_bounds__(256) void div_scalar_kernel(const float* x, int64_t
 
 __device__ __forceinline__ double track_at(const MixTracks& t, int m, int64_t j) {
     return t.is64[m] ? ((const double*)t.f0[m])[j] : (double)((const float*)t.f0[m])[j];
+}
+
+// np.interp(xq, np.arange(n), fp) for one query xq >= 0 in f64, as NumPy's arr_interp evaluates it: right of
+// xp[-1] -> fp[-1]; an exact hit (and the last node) -> fp[j]; else slope * (xq - j) + fp[j], with NumPy's two NaN
+// fallbacks (the other end point, then the common value of two equal end points).  fp(j) fetches node j as f64.
+template <typename Fetch>
+__device__ __forceinline__ double np_interp_arange(double xq, int64_t n, Fetch fp) {
+#pragma clang fp contract(off)
+    if (xq > (double)(n - 1)) return fp(n - 1);
+    int64_t j = (int64_t)floor(xq);
+    if (j > n - 1) j = n - 1;
+    const double f0 = fp(j);
+    if (j == n - 1 || (double)j == xq) return f0;
+    const double f1 = fp(j + 1);
+    const double slope = (f1 - f0) / ((double)(j + 1) - (double)j);
+    double r = slope * (xq - (double)j) + f0;
+    if (r != r) {  // numpy's NaN rescue (an infinite or NaN end point)
+        r = slope * (xq - (double)(j + 1)) + f1;
+        if (r != r && f0 == f1) r = f0;
+    }
+    return r;
 }
 
 __global__ __launch_bounds__(256) void f0_mix_kernel(MixTracks t, int64_t p_len, double* out) {
@@ -177,24 +202,7 @@ __global__ __launch_bounds__(256) void f0_mix_kernel(MixTracks t, int64_t p_len,
         // np.linspace(0, n, p_len): arange(p_len) * ((n - 0) / (p_len - 1)) + 0, the last point set to n
         const double step = (double)n / (double)(p_len - 1);
         const double xq = k == p_len - 1 ? (double)n : (double)k * step + 0.0;
-        // np.interp over xp = arange(n): right of xp[-1] -> fp[-1]
-        double r;
-        if (xq > (double)(n - 1)) r = track_at(t, m, n - 1);
-        else {
-            int64_t j = (int64_t)floor(xq);
-            if (j > n - 1) j = n - 1;
-            const double f0 = track_at(t, m, j);
-            if (j == n - 1 || (double)j == xq) r = f0;
-            else {
-                const double f1 = track_at(t, m, j + 1);
-                const double slope = (f1 - f0) / ((double)(j + 1) - (double)j);
-                r = slope * (xq - (double)j) + f0;
-                if (r != r) {  // numpy's NaN rescue (an infinite end point)
-                    r = slope * (xq - (double)(j + 1)) + f1;
-                    if (r != r && f0 == f1) r = f0;
-                }
-            }
-        }
+        const double r = np_interp_arange(xq, n, [&](int64_t j) { return track_at(t, m, j); });
         single = r;
         if (r == r) {  // nanmedian drops NaNs; insertion into the sorted prefix
             int p = cnt++;
@@ -213,13 +221,36 @@ __global__ __launch_bounds__(256) void f0_mix_kernel(MixTracks t, int64_t p_len,
     out[k] = res;
 }
 
+// get_f0_mangio_crepe's tail (convert.py:226-228) per output frame k: source[source < 0.001] = nan (an f32 compare),
+// np.interp(k * T / p_len, np.arange(T), source) in f64, np.nan_to_num
+__global__ __launch_bounds__(256) void f0_resample_nan_kernel(const float* src, int64_t T, int64_t p_len, double* out) {
+#pragma clang fp contract(off)
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= p_len) return;
+    const double xq = (double)(k * T) / (double)p_len;  // np.arange(0, T * p_len, T) / p_len
+    double r = np_interp_arange(xq, T, [&](int64_t j) {
+        const float s = src[j];
+        return s < 0.001f ? __longlong_as_double(0x7ff8000000000000ll) : (double)s;
+    });
+    if (r != r) r = 0.0;  // nan_to_num: nan -> 0, +-inf -> the largest finite f64
+    else if (r > 1.7976931348623157e308) r = 1.7976931348623157e308;
+    else if (r < -1.7976931348623157e308) r = -1.7976931348623157e308;
+    out[k] = r;
+}
+
 }  // namespace
 
 extern "C" int64_t rvc_abs_quantile_work_bytes(void) { return (int64_t)sizeof(QWork); }
 
 extern "C" int rvc_abs_quantile(const float* x, int64_t n, void* work, int64_t work_bytes, float* q_out,
                                 rvc_stream_t stream) {
+    return rvc_abs_quantile_as(x, n, RVC_QUANTILE_NUMPY, work, work_bytes, q_out, stream);
+}
+
+extern "C" int rvc_abs_quantile_as(const float* x, int64_t n, int lerp, void* work, int64_t work_bytes, float* q_out,
+                                   rvc_stream_t stream) {
     RVC_CHECK_ARG(x && work && q_out, "abs_quantile: null pointer");
+    RVC_CHECK_ARG(lerp == RVC_QUANTILE_NUMPY || lerp == RVC_QUANTILE_TORCH, "abs_quantile: unknown lerp %d", lerp);
     RVC_CHECK_ARG(n > 0 && n < (1ll << 31), "abs_quantile: bad length %lld", (long long)n);
     RVC_CHECK_ARG(work_bytes >= (int64_t)sizeof(QWork), "abs_quantile: work buffer too small");
     hipStream_t s = (hipStream_t)stream;
@@ -230,7 +261,8 @@ extern "C" int rvc_abs_quantile(const float* x, int64_t n, void* work, int64_t w
     hipLaunchKernelGGL(q_hist_kernel<1>, dim3(nb), dim3(QT), 0, s, x, n, w);
     hipLaunchKernelGGL(q_hist_kernel<2>, dim3(nb), dim3(QT), 0, s, x, n, w);
     hipLaunchKernelGGL(q_succ_kernel, dim3(nb), dim3(QT), 0, s, x, n, w);
-    hipLaunchKernelGGL(q_final_kernel, dim3(1), dim3(QT), 0, s, n, w, q_out);
+    hipLaunchKernelGGL(q_final_kernel, dim3(1), dim3(QT), 0, s, n, w, lerp == RVC_QUANTILE_TORCH ? 1 : 0,
+                       q_out);
     RVC_HIP(hipGetLastError());
     return RVC_OK;
 }
@@ -256,6 +288,16 @@ extern "C" int rvc_f0_mix(const rvc_f0_track* tracks, int M, int64_t p_len, doub
         t.is64[m] = tracks[m].is_f64;
     }
     hipLaunchKernelGGL(f0_mix_kernel, dim3(cdiv(p_len, 256)), dim3(256), 0, (hipStream_t)stream, t, p_len, out);
+    RVC_HIP(hipGetLastError());
+    return RVC_OK;
+}
+
+extern "C" int rvc_f0_resample_nan(const float* source, int64_t T, int64_t p_len, double* out, rvc_stream_t stream) {
+    RVC_CHECK_ARG(source && out, "f0_resample_nan: null pointer");
+    RVC_CHECK_ARG(T >= 1 && p_len >= 1 && T < (1ll << 31) && p_len < (1ll << 31),
+                  "f0_resample_nan: bad lengths %lld, %lld", (long long)T, (long long)p_len);
+    hipLaunchKernelGGL(f0_resample_nan_kernel, dim3(cdiv(p_len, 256)), dim3(256), 0, (hipStream_t)stream, source, T,
+                       p_len, out);
     RVC_HIP(hipGetLastError());
     return RVC_OK;
 }

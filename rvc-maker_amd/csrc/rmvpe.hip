@@ -389,8 +389,8 @@ __device__ float np_pairwise9_f(const float* a) {
 }
 
 __global__ void rmvpe_decode_kernel(const float* sal, int64_t ld, int64_t F, double thred, double shift,
-                                    double mel_min, double mel_max, rvc_f0_post post, double* f0_out, int64_t* coarse,
-                                    float* pitchf) {
+                                    double f0_min, double f0_max, double mel_min, double mel_max, rvc_f0_post post,
+                                    double* f0_out, int64_t* coarse, float* pitchf) {
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= F) return;
     int am = 0;
@@ -415,21 +415,30 @@ __global__ void rmvpe_decode_kernel(const float* sal, int64_t ld, int64_t F, dou
     if ((double)fmaxf(mx, 0.f) <= thred) dev = 0.0;
     double f0 = 10.0 * pow(2.0, dev / 1200.0);
     if (f0 == 10.0) f0 = 0.0;
+    // infer_from_audio_with_pitch (RMVPE.py:232): never true for the unbounded (-inf, +inf) of rvc_rmvpe_decode
+    if (f0 < f0_min || f0 > f0_max) f0 = 0.0;
     f0 = f0_post_apply<double>(f0, t, shift, post);
     if (f0_out) f0_out[t] = f0;
     coarse[t] = f0_coarse(f0, mel_min, mel_max);
     pitchf[t] = (float)f0;
 }
 
-extern "C" int rvc_rmvpe_decode(const float* sal, int64_t ld, int64_t F, double thred, double shift,
-                                const rvc_f0_post* post, double* f0, int64_t* coarse, float* pitchf,
-                                rvc_stream_t stream) {
+extern "C" int rvc_rmvpe_decode_range(const float* sal, int64_t ld, int64_t F, double thred, double f0_min,
+                                      double f0_max, double shift, const rvc_f0_post* post, double* f0,
+                                      int64_t* coarse, float* pitchf, rvc_stream_t stream) {
     RVC_CHECK_ARG(sal && coarse && pitchf && F > 0 && ld >= F, "rmvpe_decode: bad args");
+    RVC_CHECK_ARG(f0_min == f0_min && f0_max == f0_max, "rmvpe_decode: NaN f0 range");
     RVC_CHECK_ARG(!post || !post->rep || (post->rep_off >= 0 && post->rep_len >= 0), "rmvpe_decode: bad f0 post");
     const rvc_f0_post pp = f0_post_or_none(post);
     const F0MelRange mel = f0_mel_range();
     hipLaunchKernelGGL(rmvpe_decode_kernel, dim3(cdiv(F, 128)), dim3(128), 0, (hipStream_t)stream, sal, ld, F, thred,
-                       shift, mel.min, mel.max, pp, f0, coarse, pitchf);
+                       shift, f0_min, f0_max, mel.min, mel.max, pp, f0, coarse, pitchf);
     RVC_HIP(hipGetLastError());
     return RVC_OK;
+}
+
+extern "C" int rvc_rmvpe_decode(const float* sal, int64_t ld, int64_t F, double thred, double shift,
+                                const rvc_f0_post* post, double* f0, int64_t* coarse, float* pitchf,
+                                rvc_stream_t stream) {
+    return rvc_rmvpe_decode_range(sal, ld, F, thred, -INFINITY, INFINITY, shift, post, f0, coarse, pitchf, stream);
 }

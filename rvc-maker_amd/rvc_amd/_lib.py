@@ -173,8 +173,10 @@ SIGNATURES = {
     "rvc_swipe_post": [c_void_p, c_int64, c_float, POINTER(F0Post), c_void_p, c_void_p, c_void_p],
     "rvc_abs_quantile_work_bytes": [],
     "rvc_abs_quantile": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
+    "rvc_abs_quantile_as": [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p],
     "rvc_div_scalar": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     "rvc_f0_mix": [POINTER(F0Track), c_int, c_int64, c_void_p, c_void_p],
+    "rvc_f0_resample_nan": [c_void_p, c_int64, c_int64, c_void_p, c_void_p],
     "rvc_fcpe_mel": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p],
     "rvc_groupnorm_work_bytes": [c_int64, c_int],
     "rvc_groupnorm_act": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_float, c_float,
@@ -254,6 +256,8 @@ SIGNATURES = {
                             c_int64, c_void_p],
     "rvc_rmvpe_decode": [c_void_p, c_int64, c_int64, c_double, c_double, POINTER(F0Post), c_void_p, c_void_p,
                          c_void_p, c_void_p],
+    "rvc_rmvpe_decode_range": [c_void_p, c_int64, c_int64, c_double, c_double, c_double, c_double, POINTER(F0Post),
+                               c_void_p, c_void_p, c_void_p, c_void_p],
     "rvc_filtfilt_work_bytes": [c_int64],
     "rvc_filtfilt_pad": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                          c_void_p],
@@ -287,6 +291,8 @@ SIGNATURES = {
     "rvc_crepe_decode_ws_bytes": [c_int64],
     "rvc_crepe_decode": [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_void_p,
                          c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    "rvc_crepe_decode_as": [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_void_p,
+                            c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     "rvc_crepe_smooth_coarse": [c_void_p, c_void_p, c_int64, c_float, c_double, c_double, POINTER(F0Post), c_void_p,
                                 c_void_p, c_void_p],
     "rvc_phone_upsample": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_void_p],

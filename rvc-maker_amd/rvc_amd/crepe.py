@@ -29,6 +29,7 @@ from .synthetic import CREPE_CAPACITY
 HOP = 160
 BATCH = 512  # get_f0_crepe's predict(batch_size=512): the Viterbi runs per batch
 BN_EPS = 0.0010000000474974513
+HZ_POWF, HZ_TORCH = 0, 1  # RVC_CREPE_HZ_*: whose power of two bins -> Hz takes
 
 
 def _freq_to_bin(f, quantize):
@@ -68,12 +69,13 @@ class CrepeAMD:
         return cls(torch.load(path, map_location="cpu", weights_only=True), capacity, device)
 
     # ------------------------------------------------------------------ network
-    def probabilities(self, audio: torch.Tensor, frame0: int, nb: int, out: torch.Tensor):
-        """Sigmoid outputs of frames [frame0, frame0 + nb) into out [360][nb] (a strided view is fine)."""
+    def probabilities(self, audio: torch.Tensor, frame0: int, nb: int, out: torch.Tensor, hop: int = HOP):
+        """Sigmoid outputs of frames [frame0, frame0 + nb) at hop ``hop`` into out [360][nb] (a strided view is
+        fine)."""
         lib = _lib.load()
         dev = audio.device
         frames = torch.empty(nb, 1024, device=dev)
-        check(lib.rvc_crepe_frames(ops._p(audio), audio.numel(), HOP, frame0, nb, ops._p(frames), ops._stream()),
+        check(lib.rvc_crepe_frames(ops._p(audio), audio.numel(), int(hop), frame0, nb, ops._p(frames), ops._stream()),
               "crepe_frames")
         x, L = frames, 1024
         for i in range(6):
@@ -98,40 +100,86 @@ class CrepeAMD:
         self.classifier(x, out=out, out_act=ACT_SIGMOID)
 
     # ------------------------------------------------------------------ f0
+    def _all_probabilities(self, audio, T, hop=HOP):
+        """The network over frames 0..T-1 at hop ``hop``, BATCH frames a pass -> probs [360][T]."""
+        probs = torch.empty(360, T, device=audio.device)
+        for a in range(0, T, BATCH):
+            b = min(a + BATCH, T)
+            pb = torch.empty(360, b - a, device=audio.device)
+            self.probabilities(audio, a, b - a, pb, hop)
+            probs[:, a:b] = pb
+        return probs
+
+    def _dither(self, T, dev):
+        """The T triangular draws of bins_to_frequency (CREPE.py:118), in frame order, as device f32."""
+        if self.dither_fn is not None:
+            dither = np.asarray(self.dither_fn(T), dtype=np.float64)
+        elif ops.graph_mode():  # captured pass: the same triangular law drawn on the device (graph.py)
+            return ops.rand_triang(torch.empty(T, device=dev), -20.0, 20.0, 0x43524550, 0)
+        else:  # scipy.stats.triang.rvs(c=0.5, loc=-20, scale=40): numpy's triangular on [-20, 20]
+            dither = np.random.triangular(-20.0, 0.0, 20.0, size=T)
+        return torch.from_numpy(dither.astype(np.float32)).to(dev)
+
+    def _decode(self, probs, seq, dither_d, hz=HZ_POWF):
+        """rvc_crepe_decode of probs [360][T] (masked in place) with the Viterbi restarted at the frame offsets
+        ``seq`` (0, ..., T) -> (f0_raw f32 [T], pd_raw f32 [T]); ``hz`` = HZ_TORCH: bins -> Hz with the power of two of
+        torch's vector path (rvc_crepe_decode_as; HZ_POWF is rvc_crepe_decode)."""
+        dev, T = probs.device, probs.shape[1]
+        lib = _lib.load()
+        need = lib.rvc_crepe_decode_ws_bytes(T)
+        ws = ops._workspace(dev, need, "crepe")
+        key = (str(dev), T, seq[1])  # offsets resident per length and batch (no host copy inside a captured pass)
+        seq_off = self.__dict__.setdefault("_seq_off", {}).get(key)
+        if seq_off is None:
+            seq_off = self._seq_off[key] = torch.tensor(seq, dtype=torch.int64, device=dev)
+        f0r = torch.empty(T, device=dev)
+        pdr = torch.empty(T, device=dev)
+        check(lib.rvc_crepe_decode_as(ops._p(probs), T, self.lo, self.hi, ops._p(seq_off), len(seq) - 1,
+                                      ctypes_ptr(self.log_trans), self.log_off, self.log_p_init, ops._p(dither_d),
+                                      int(hz), ops._p(ws), need, ops._p(f0r), ops._p(pdr), ops._stream()),
+              "crepe_decode")
+        return f0r, pdr
+
+    def decode_mangio(self, probs, hop_length, p_len, trace=None):
+        """get_f0_mangio_crepe from the network's output on (convert.py:225-228; CREPE.py:105-109, 137-149): probs
+        device f32 [360][T] (sigmoid outputs, masked in place) -> raw f0 f64 [p_len].  predict(batch_size = 2 *
+        hop_length) decodes per batch, so the Viterbi restarts every 2 * hop_length frames; the dither is drawn in
+        frame order, bins -> Hz with the power of two of torch's vector path (HZ_TORCH: the reference's value but on
+        the tail frames of a batch, which torch computes with the C library's powf); no periodicity, smoothing or
+        gate; then rvc_f0_resample_nan.  (The GPU tests decode the
+        reference's recorded probabilities through here.)"""
+        hop_length = int(hop_length)
+        if hop_length < 1:
+            raise ValueError(f"mangio-crepe: hop_length {hop_length} < 1")
+        T = probs.shape[1]
+        seq = list(range(0, T, 2 * hop_length)) + [T]
+        f0r, _ = self._decode(probs, seq, self._dither(T, probs.device), HZ_TORCH)
+        if trace is not None:
+            trace["f0_raw"] = f0r.cpu().numpy()
+        return ops.f0_resample_nan(f0r, p_len)
+
+    def f0_mangio(self, x32: torch.Tensor, hop_length: int, p_len: int, trace=None):
+        """VC.get_f0_mangio_crepe (convert.py:215-228) without its normalisation (the caller's): x32 device f32 [N]
+        -> raw f0 f64 [p_len]; 1 + N // hop_length frames at hop ``hop_length``."""
+        hop_length = int(hop_length)
+        if hop_length < 1:
+            raise ValueError(f"mangio-crepe: hop_length {hop_length} < 1")
+        probs = self._all_probabilities(x32, 1 + x32.numel() // hop_length, hop_length)
+        if trace is not None:
+            trace["probs"] = probs.t().cpu().numpy().copy()
+        return self.decode_mangio(probs, hop_length, p_len, trace)
+
     def f0_device(self, audio: torch.Tensor, pitch_shift: float = 0.0, trace=None, post=None):
         """audio [N] device f32 (the padded 16 kHz signal) -> (coarse int64 [T], pitchf f32 [T]),
         T = 1 + N // 160."""
         dev = audio.device
         N = audio.numel()
         T = 1 + N // HOP
-        probs = torch.empty(360, T, device=dev)
-        seq = list(range(0, T, BATCH)) + [T]
-        for a, b in zip(seq[:-1], seq[1:]):
-            pb = torch.empty(360, b - a, device=dev)
-            self.probabilities(audio, a, b - a, pb)
-            probs[:, a:b] = pb
+        probs = self._all_probabilities(audio, T)
         if trace is not None:
             trace["probs"] = probs.t().cpu().numpy().copy()
-        if self.dither_fn is not None:
-            dither = np.asarray(self.dither_fn(T), dtype=np.float64)
-            dither_d = torch.from_numpy(dither.astype(np.float32)).to(dev)
-        elif ops.graph_mode():  # captured pass: the same triangular law drawn on the device (graph.py)
-            dither_d = ops.rand_triang(torch.empty(T, device=dev), -20.0, 20.0, 0x43524550, 0)
-        else:  # scipy.stats.triang.rvs(c=0.5, loc=-20, scale=40): numpy's triangular on [-20, 20]
-            dither = np.random.triangular(-20.0, 0.0, 20.0, size=T)
-            dither_d = torch.from_numpy(dither.astype(np.float32)).to(dev)
+        f0r, pdr = self._decode(probs, list(range(0, T, BATCH)) + [T], self._dither(T, dev))
         lib = _lib.load()
-        need = lib.rvc_crepe_decode_ws_bytes(T)
-        ws = ops._workspace(dev, need, "crepe")
-        key = (str(dev), T)  # batch offsets, resident per length (no host copy inside a captured pass)
-        seq_off = self.__dict__.setdefault("_seq_off", {}).get(key)
-        if seq_off is None:
-            seq_off = self._seq_off[key] = torch.tensor(seq, dtype=torch.int64, device=dev)
-        f0r = torch.empty(T, device=dev)
-        pdr = torch.empty(T, device=dev)
-        check(lib.rvc_crepe_decode(ops._p(probs), T, self.lo, self.hi, ops._p(seq_off), len(seq) - 1,
-                                   ctypes_ptr(self.log_trans), self.log_off, self.log_p_init, ops._p(dither_d),
-                                   ops._p(ws), need, ops._p(f0r), ops._p(pdr), ops._stream()), "crepe_decode")
         coarse = torch.empty(T, dtype=torch.int64, device=dev)
         pitchf = torch.empty(T, device=dev)
         mel_min = 1127 * np.log(1 + 50 / 700)

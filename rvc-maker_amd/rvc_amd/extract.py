@@ -14,12 +14,13 @@ files are the only output, so there is no data-path collective, only a barrier b
 the file list.  Host-side steps (coarse quantiser, file naming, list building) follow the reference
 expression for expression; ``tests/golden/edges.npz`` pins ``coarse_f0`` against it.
 
-f0 methods on the device: ``rmvpe``, ``crepe-{tiny,...,full}``, ``swipe``, ``fcpe``, ``fcpe-legacy`` (when its
-model is given or ``FeatureInputAMD.FCPE_LEGACY_PT`` exists) and ``hybrid[a+b+...]`` over those and ``pm``
-(the reference's other estimators -- harvest, dio, yin, pyin, ... -- are third-party or off the path and
-raise).  The estimators, their loaders and the members' raw tracks are f0.py's ``F0Bank``, shared with the
-conversion path's ``VC``; ``compute_f0`` copies the signal to the device and the track back.  Embedders: fairseq
-ContentVec (``embedders_mode="fairseq"``).
+f0 methods on the device: ``rmvpe``, ``rmvpe-legacy``, ``crepe-{tiny,...,full}``,
+``mangio-crepe-{tiny,...,full}``, ``swipe``, ``fcpe``, ``fcpe-legacy`` (when its model is given or
+``FeatureInputAMD.FCPE_LEGACY_PT`` exists) and ``hybrid[a+b+...]`` over those and ``pm`` (the reference's
+other estimators -- harvest, dio, yin, pyin -- are third-party or off the path and raise). The estimators,
+their loaders and the members' raw tracks are f0.py's ``F0Bank``, shared with the conversion path's ``VC``;
+``compute_f0`` copies the signal to the device and the track back. Embedders: fairseq ContentVec
+(``embedders_mode="fairseq"``).
 """
 from __future__ import annotations
 
@@ -56,20 +57,27 @@ class FeatureInputAMD(F0Bank):
 
     def compute_f0(self, np_arr, f0_method, hop_length=160, f0_onnx=False):
         """extract.py:149-151 for the device methods, each as F0Bank.f0_raw returns it, on the host: rmvpe f64
-        [1 + N//160] (RMVPE.infer_from_audio, thred 0.03), crepe-<cap> and swipe f32 [1 + N//160], fcpe and fcpe-legacy
-        f64 [N // 160] (the two that read ``hop_length``); hybrid[...] see compute_f0_hybrid."""
+        [1 + N//160] (RMVPE.infer_from_audio, thred 0.03; rmvpe-legacy: infer_from_audio_with_pitch), crepe-<cap> and
+        swipe f32 [1 + N//160], fcpe, fcpe-legacy and mangio-crepe-<cap> f64 [N // 160] (the three that read
+        ``hop_length``); hybrid[...] see compute_f0_hybrid."""
         if f0_onnx:
             raise NotImplementedError(f"f0 method {f0_method!r} (onnx) is not on the device path")
         self.check_f0_method(f0_method)  # raises for what is not on the device path, before any device work
         if "hybrid" in f0_method:
             return self.compute_f0_hybrid(f0_method, np_arr, hop_length)
         f0 = self.f0_raw(self._dev32(np_arr), f0_method, np_arr.size // self.hop, hop_length).cpu().numpy()
-        if f0_method == "rmvpe":
+        if f0_method in ("rmvpe", "rmvpe-legacy"):
             self.rmvpe.check_error()  # the BiGRU's hand-off timeout, as RMVPE.infer_from_audio checks it
         return f0
 
     def _dev32(self, np_arr):
         return torch.from_numpy(np.copy(np_arr).astype(np.float32)).to(self.device)
+
+    def _mangio_scale(self, x32):
+        """get_mangio_crepe (extract.py:165-166) divides by torch.quantile(|x|, 0.999), whose lerp is fused: not
+        NumPy's value to the bit (f0mix.QUANTILE_TORCH)."""
+        from . import f0mix
+        return f0mix.normalize(x32.contiguous(), f0mix.QUANTILE_TORCH)
 
     def compute_f0_hybrid(self, f0_method, np_arr, hop_length=160):
         """extract.py:132-147: the members' raw tracks on the signal as it is (no quantile normalisation, unlike
@@ -81,7 +89,7 @@ class FeatureInputAMD(F0Bank):
         x32 = self._dev32(np_arr)
         x64 = torch.from_numpy(np.asarray(np_arr, np.float64)).to(self.device) if "pm" in members else None
         f0 = f0mix.mix([self.f0_raw(x32, m, p_len, hop_length, x64) for m in members], p_len).cpu().numpy()
-        if "rmvpe" in members:
+        if "rmvpe" in members or "rmvpe-legacy" in members:
             self.rmvpe.check_error()
         return f0
 

@@ -13,11 +13,14 @@ import torch
 
 PREDICTORS = os.path.join("assets", "models", "predictors")
 CREPE_METHODS = {f"crepe-{c}": c for c in ("tiny", "small", "medium", "large", "full")}  # method -> capacity
-METHODS = ("rmvpe", "pm", "swipe", "fcpe", "fcpe-legacy")  # the single methods beside crepe-*
+# mangio-crepe-<capacity>: the same network behind get_f0_mangio_crepe's framing and decode (method -> capacity)
+MANGIO_METHODS = {f"mangio-crepe-{c}": c for c in CREPE_METHODS.values()}
+RMVPE_LEGACY = "rmvpe-legacy"  # rmvpe with the decoded f0 outside f0_min..f0_max zeroed
+METHODS = ("rmvpe", RMVPE_LEGACY, "pm", "swipe", "fcpe", "fcpe-legacy")  # the single methods beside *crepe-*
 HYBRID_EXTRA = ("fcpe",)  # hybrid members beyond f0mix.MEMBERS that need a model the holder always has or can load
 LEGACY = "fcpe-legacy"  # a method, and a hybrid member, only while its model is at hand (F0Bank._fcpe_legacy)
 ON_PATH = ", ".join(m for m in METHODS if m != LEGACY) + \
-          f", crepe-*, {LEGACY} (with its model) and hybrid[...] over them"
+          f", crepe-*, mangio-crepe-*, {LEGACY} (with its model) and hybrid[...] over them"
 
 
 def refuse(what, name, why="is not on the device path"):
@@ -31,6 +34,7 @@ class F0Bank:
     The holder provides ``self.device``, ``self.f0_min`` and ``self.f0_max``."""
 
     CREPE_METHODS = CREPE_METHODS
+    MANGIO_METHODS = MANGIO_METHODS
     HYBRID_EXTRA = HYBRID_EXTRA
     FCPE_LEGACY_PT = os.path.join(PREDICTORS, "fcpe_legacy.pt")
     MEMBER_ONLY = ()  # methods this holder takes as hybrid members but not alone
@@ -105,17 +109,31 @@ class F0Bank:
             self._fcpe_legacy()
         elif f0_method in self.MEMBER_ONLY:
             refuse("f0 method", f0_method, "is taken only as a hybrid member here")
-        elif f0_method not in METHODS and f0_method not in CREPE_METHODS:
+        elif f0_method not in METHODS and f0_method not in CREPE_METHODS and f0_method not in MANGIO_METHODS:
             refuse("f0 method", f0_method)
 
     # ------------------------------------------------------------------ raw tracks
+    def _mangio_scale(self, x32):
+        """x / np.quantile(|x|, 0.999) as VC.get_f0_mangio_crepe takes it (NumPy's f32 quantile; rvc_abs_quantile).
+        extract.FeatureInputAMD overrides it: get_mangio_crepe divides by torch.quantile."""
+        from . import f0mix
+        return f0mix.normalize(x32.contiguous())
+
     def f0_raw(self, x32, member, p_len, hop_length=64, x64=None):
         """One estimator's raw track (before any shift / autotune) on the device f32 signal x32, as the reference's
         members return it: rmvpe f64 [1 + N//160], crepe-* f32 [1 + N//160], pm f64 padded to p_len (Praat reads the
         f64 samples ``x64``, by default x32 promoted), swipe f32 [1 + N//160], fcpe and fcpe-legacy f64 [p_len]
-        (the two that read ``hop_length``)."""
+        (the two that read ``hop_length``), rmvpe-legacy as rmvpe, mangio-crepe-* f64 [p_len] (reads ``hop_length``
+        too).  ``_mangio_scale`` is the holder's own normalisation of mangio's input."""
         if member == "rmvpe":
             return self._rmvpe().f0_device(x32, 0.03, 0.0, want_f0=True)[2]
+        if member == RMVPE_LEGACY:
+            # get_f0_rmvpe(legacy=True) (convert.py:248-255): f0[(f0 < f0_min) | (f0 > f0_max)] = 0 in the decode
+            return self._rmvpe().f0_device(x32, 0.03, 0.0, want_f0=True, f0_range=(self.f0_min, self.f0_max))[2]
+        if member in MANGIO_METHODS:
+            # get_f0_mangio_crepe (convert.py:215-228) divides its input by the 0.999 |x| quantile itself: inside a
+            # hybrid of the conversion path that is a second division
+            return self._crepe(MANGIO_METHODS[member]).f0_mangio(self._mangio_scale(x32), int(hop_length), p_len)
         if member in CREPE_METHODS:
             # shift 2^0 = 1 and no post: pitchf is the raw f0
             return self._crepe(CREPE_METHODS[member]).f0_device(x32, 0.0)[1]

@@ -13,7 +13,9 @@ import torch
 from . import _lib, f0, ops
 
 CREPE_MEMBERS = tuple(f0.CREPE_METHODS)
-MEMBERS = ("rmvpe", "pm", "swipe") + CREPE_MEMBERS  # the members that need no model, or one every holder can load
+MANGIO_MEMBERS = tuple(f0.MANGIO_METHODS)
+# the members that need no model, or one every holder can load (rmvpe.pt, crepe_<capacity>.pth)
+MEMBERS = ("rmvpe", f0.RMVPE_LEGACY, "pm", "swipe") + CREPE_MEMBERS + MANGIO_MEMBERS
 MAX_TRACKS = 8
 
 
@@ -45,19 +47,25 @@ def _f32(x):
     return ctypes.c_void_p(x.data_ptr())
 
 
-def abs_quantile(x: torch.Tensor) -> torch.Tensor:
-    """np.quantile(np.abs(x), 0.999) of a device f32 signal -> device f32 [1]."""
+QUANTILE_NUMPY, QUANTILE_TORCH = 0, 1  # RVC_QUANTILE_*: whose lerp between the two order statistics
+
+
+def abs_quantile(x: torch.Tensor, lerp: int = QUANTILE_NUMPY) -> torch.Tensor:
+    """np.quantile(np.abs(x), 0.999) of a device f32 signal -> device f32 [1]; QUANTILE_TORCH: torch.quantile's
+    value (its lerp is one fused multiply-add; extract.py:166)."""
     lib = _lib.load()
     q = torch.empty(1, dtype=torch.float32, device=x.device)
     need = lib.rvc_abs_quantile_work_bytes()
     work = ops._workspace(x.device, need, "quantile")
-    ops.check(lib.rvc_abs_quantile(_f32(x), x.numel(), ops._p(work), need, _f32(q), ops._stream()), "abs_quantile")
+    ops.check(lib.rvc_abs_quantile_as(_f32(x), x.numel(), int(lerp), ops._p(work), need, _f32(q), ops._stream()),
+              "abs_quantile")
     return q
 
 
-def normalize(x: torch.Tensor) -> torch.Tensor:
-    """x / np.quantile(np.abs(x), 0.999) in f32 (get_f0_hybrid's input normalisation), on the device."""
-    q = abs_quantile(x)
+def normalize(x: torch.Tensor, lerp: int = QUANTILE_NUMPY) -> torch.Tensor:
+    """x / np.quantile(np.abs(x), 0.999) in f32 (get_f0_hybrid's and get_f0_mangio_crepe's input normalisation), on
+    the device; QUANTILE_TORCH: x / torch.quantile(torch.abs(x), 0.999) (FeatureInput.get_mangio_crepe)."""
+    q = abs_quantile(x, lerp)
     out = torch.empty_like(x)
     ops.check(_lib.load().rvc_div_scalar(_f32(x), x.numel(), _f32(q), _f32(out), ops._stream()), "div_scalar")
     return out

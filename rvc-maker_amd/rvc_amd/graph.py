@@ -24,7 +24,7 @@ class ClipGraph:
     ``out`` is a view of the graph's static output buffer, overwritten by the next replay."""
 
     def __init__(self, vc, model, net_g, sid, n_samples: int, pitch=0, version="v2", protect=0.33, index=None,
-                 index_rate=0.0, f0_method="rmvpe", volume_envelope=1.0, warmup: int = 1):
+                 index_rate=0.0, f0_method="rmvpe", volume_envelope=1.0, warmup: int = 1, hop_length=64):
         if n_samples + vc.window > vc.t_max:
             raise ValueError(f"ClipGraph: a {n_samples}-sample clip is segmented on the host (> t_max); "
                              "split it into chunks first")
@@ -36,7 +36,7 @@ class ClipGraph:
         self.inp = torch.zeros(self.n, device=dev)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
         args = (model, net_g, sid, self.inp, pitch, version, protect, index, index_rate, f0_method)
-        kw = dict(volume_envelope=volume_envelope)
+        kw = dict(volume_envelope=volume_envelope, hop_length=hop_length)  # hop_length: fcpe*, mangio-crepe-*
         seed0, vc.seed = vc.seed, 0  # the captured seed is 0 + the device seed
         prio0, vc.side_priority = getattr(vc, "side_priority", None), 0  # normal-priority fork in graphs
         try:

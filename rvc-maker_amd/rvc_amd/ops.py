@@ -988,10 +988,29 @@ def f0_post64(f0, p_len, pitch, post=None):
     return coarse, pitchf
 
 
-def rmvpe_decode(sal, ld, F, thred, shift, f0, coarse, pitchf, post=None):
+def f0_resample_nan(source, p_len):
+    """get_f0_mangio_crepe's tail (convert.py:226-228; rvc_f0_resample_nan): source device f32 [T] -> f64 [p_len],
+    np.nan_to_num(np.interp(np.arange(0, T * p_len, T) / p_len, np.arange(T), source)) with source < 0.001 as NaN."""
+    if not source.is_cuda or source.dtype != torch.float32 or source.dim() != 1 or not source.is_contiguous():
+        raise TypeError(f"f0_resample_nan: expected a contiguous 1-D CUDA f32 tensor, got {source.dtype} "
+                        f"{tuple(source.shape)} on {source.device}")
+    out = torch.empty(int(p_len), dtype=torch.float64, device=source.device)
+    check(_lib.load().rvc_f0_resample_nan(_p(source), source.numel(), int(p_len), _pd(out), _stream()),
+          "f0_resample_nan")
+    return out
+
+
+def rmvpe_decode(sal, ld, F, thred, shift, f0, coarse, pitchf, post=None, f0_range=None):
+    """rvc_rmvpe_decode; ``f0_range`` = (f0_min, f0_max) zeroes the decoded f0 outside it first (rmvpe-legacy,
+    rvc_rmvpe_decode_range)."""
     if sal.numel() < 360 * ld or coarse.numel() < F or pitchf.numel() < F or (f0 is not None and f0.numel() < F):
         raise ValueError("rmvpe_decode: size mismatch")
     f0p = ctypes.c_void_p(f0.data_ptr()) if f0 is not None else None
+    if f0_range is not None:
+        check(_lib.load().rvc_rmvpe_decode_range(_p(sal), ld, F, thred, float(f0_range[0]), float(f0_range[1]), shift,
+                                                 _post_ref(post, F), f0p, _p(coarse), _p(pitchf), _stream()),
+              "rmvpe_decode_range")
+        return
     check(_lib.load().rvc_rmvpe_decode(_p(sal), ld, F, thred, shift, _post_ref(post, F), f0p, _p(coarse), _p(pitchf),
                                        _stream()), "rmvpe_decode")
 

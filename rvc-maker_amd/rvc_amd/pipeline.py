@@ -18,11 +18,12 @@ releases the streams the library created for it.
 FAISS retrieval (``file_index`` + ``index_rate``) runs on the device (retrieval.py / ivf.hip); the
 index file is read without faiss (faiss_index.py) and kept resident per path.
 
-f0 methods, all on the device: "rmvpe", "crepe-{tiny,small,medium,large,full}" (crepe.py), "pm" (pm.py),
-"swipe" (swipe.py), "fcpe" (fcpe.py), "fcpe-legacy" (fcpe_legacy.py; only while its model is at hand) and
-"hybrid[a+b+...]" over those (f0mix.py: the members' raw tracks resampled and their nanmedian taken, as
-get_f0_hybrid).  The list of names, the loaders and the members' raw tracks (``f0_raw``) are f0.py's; ``f0_device``
-here adds each method's own post step (shift, autotune, f0 file, mel quantiser).
+f0 methods, all on the device: "rmvpe", "rmvpe-legacy", "crepe-{tiny,small,medium,large,full}" and
+"mangio-crepe-{...}" (crepe.py), "pm" (pm.py), "swipe" (swipe.py), "fcpe" (fcpe.py), "fcpe-legacy" (fcpe_legacy.py;
+only while its model is at hand) and "hybrid[a+b+...]" over those (f0mix.py: the members' raw tracks
+resampled and their nanmedian taken, as get_f0_hybrid). The list of names, the loaders and the members' raw
+tracks (``f0_raw``) are f0.py's; ``f0_device`` here adds each method's own post step (shift, autotune, f0
+file, mel quantiser).
 
 f0 autotune and f0 files run inside the f0 decode kernels; volume_envelope != 1 (change_rms) runs on
 the device after the segment loop.  Embedders: fairseq ``.pt`` and transformers ``.safetensors``
@@ -40,7 +41,7 @@ from scipy import signal
 
 from . import contentvec as cvm
 from . import f0mix, ops
-from .f0 import F0Bank
+from .f0 import RMVPE_LEGACY, F0Bank
 
 BH, AH = signal.butter(N=5, Wn=48, btype="high", fs=16000)  # convert.py:30
 
@@ -142,19 +143,21 @@ class VC(F0Bank):
         """VC.get_f0 (convert.py:304-323) on the device: (coarse int64 [T], pitchf f32 [T]).  Autotune
         and the f0-file override run inside the decode kernels, in the reference's order.  "pm" reads the
         f64 signal ``xp64`` (the reference hands parselmouth the f64 filtfilt output); ``hop_length`` is the one
-        ``pipeline`` receives, which only "fcpe" and "fcpe-legacy" (alone or as hybrid members) read.
+        ``pipeline`` receives, which only "fcpe", "fcpe-legacy" and "mangio-crepe-*" (alone or as hybrid members)
+        read.
 
-        rmvpe, crepe-* and swipe end in post kernels of their own (rvc_rmvpe_decode in f64, rvc_crepe_smooth_coarse
-        and rvc_swipe_post in f32, as NumPy promotes in the reference); pm, fcpe, fcpe-legacy and the hybrids end in
-        the f64 ops.f0_post64."""
+        rmvpe, rmvpe-legacy, crepe-* and swipe end in post kernels of their own (rvc_rmvpe_decode[_range] in f64,
+        rvc_crepe_smooth_coarse and rvc_swipe_post in f32, as NumPy promotes in the reference); pm, fcpe, fcpe-legacy,
+        mangio-crepe-* and the hybrids end in the f64 ops.f0_post64."""
         self.check_f0_method(f0_method)  # raises for what is not on the device path, before any device work
         post = None
         if f0_autotune or inp_f0 is not None:
             rep, off = f0_override(inp_f0, self.x_pad) if inp_f0 is not None else (None, 0)
             post = ops.F0Post(f0_autotune_strength if f0_autotune else None, rep, off, xp.device)
         p_len = xp.numel() // self.window
-        if f0_method == "rmvpe":
-            coarse, pitchf, _ = self._rmvpe().f0_device(xp, 0.03, float(pitch), post=post)
+        if f0_method in ("rmvpe", RMVPE_LEGACY):  # legacy's range filter sits in the decode, before shift and autotune
+            coarse, pitchf, _ = self._rmvpe().f0_device(xp, 0.03, float(pitch), post=post,
+                                                        f0_range=self._rmvpe_range(f0_method))
             return coarse, pitchf
         if f0_method in self.CREPE_METHODS:
             return self._crepe(self.CREPE_METHODS[f0_method]).f0_device(xp, float(pitch), post=post)
@@ -171,9 +174,14 @@ class VC(F0Bank):
             # the raw tracks are resampled to p_len and their nanmedian taken, in f64
             xn = f0mix.normalize(xp.contiguous())
             f0 = f0mix.mix([self.f0_raw(xn, m, p_len, hop_length) for m in self.f0_members(f0_method)], p_len)
-        else:  # "fcpe" / "fcpe-legacy": the raw track of get_f0_fcpe on the signal as it is
+        else:  # "fcpe" / "fcpe-legacy": the raw track of get_f0_fcpe on the signal as it is; "mangio-crepe-*": of
+            # get_f0_mangio_crepe, which divides the signal by its quantile itself (f0mix.normalize, in f0_raw)
             f0 = self.f0_raw(xp.contiguous(), f0_method, p_len, hop_length)
         return ops.f0_post64(f0, p_len, float(pitch), post)
+
+    def _rmvpe_range(self, f0_method):
+        """The decode's f0 range: rmvpe-legacy's f0_min..f0_max filter, None for rmvpe."""
+        return (self.f0_min, self.f0_max) if f0_method == RMVPE_LEGACY else None
 
     # ------------------------------------------------------------------ device pieces
     def features_device(self, model, a0, version):
@@ -299,14 +307,15 @@ class VC(F0Bank):
                                         index_rate, f0_method, f0_opts, volume_envelope, src64, xp64)
 
     def pipeline_device_batch(self, model, net_g, sid, audios, pitch, version, protect, index=None, index_rate=0.0,
-                              f0_method="rmvpe"):
+                              f0_method="rmvpe", hop_length=64):
         """``pipeline_device`` over B equal-length clips at once (the chunk loop of convert.py:506-507 for
         equal-length chunks, BASELINE configs[2]): RMVPE (U-Net, W_ih, the B BiGRU recurrences side by side)
         and ContentVec run as B-batched launches on their two streams, then the synthesizer as B-clip launches
         (``voice_conversion_batch_device``; RVC_AMD_SYNTH_BATCH=0: per clip).  Clip b draws its noise with seed
         ``self.seed + b``: it equals ``pipeline_device`` of that clip with ``seed = self.seed + b``, up to the
-        summation order of the batched launches (split-K / split-KV follow the batched grid).  Clips must fit one segment
-        (N + window <= t_max, 41 s)."""
+        summation order of the batched launches (split-K / split-KV follow the batched grid).  Clips must fit one
+        segment (N + window <= t_max, 41 s).  "rmvpe-legacy" batches as "rmvpe" does; ``hop_length`` goes to the f0
+        methods that read it (``f0_device``)."""
         B = len(audios)
         audios = [a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(
             self.device) for a in audios]
@@ -321,10 +330,11 @@ class VC(F0Bank):
         ready.record(main)
         with torch.cuda.stream(side):
             side.wait_event(ready)
-            if f0_method == "rmvpe":
-                coarse, pitchf = self._rmvpe().f0_device_batch(xpb, 0.03, float(pitch))
+            if f0_method in ("rmvpe", RMVPE_LEGACY):
+                coarse, pitchf = self._rmvpe().f0_device_batch(xpb, 0.03, float(pitch),
+                                                               f0_range=self._rmvpe_range(f0_method))
             else:
-                pairs = [self.f0_device(xpb[b], pitch, f0_method) for b in range(B)]
+                pairs = [self.f0_device(xpb[b], pitch, f0_method, hop_length=hop_length) for b in range(B)]
                 coarse, pitchf = torch.stack([c for c, _ in pairs]), torch.stack([f for _, f in pairs])
             f0_done = torch.cuda.Event()
             f0_done.record(side)
@@ -355,7 +365,7 @@ class VC(F0Bank):
         return outs
 
     def pipeline_device_stream(self, model, net_g, sid, audios, pitch, version, protect, index=None, index_rate=0.0,
-                               f0_method="rmvpe", batch=1, events=None, seeds=None, host_out=None):
+                               f0_method="rmvpe", batch=1, events=None, seeds=None, host_out=None, hop_length=64):
         """``pipeline_device`` over a sequence of clips (the file / chunk loops of convert.py:129-135 and
         :506-507) with clip k+1's front end -- filtfilt, f0 on the side stream, ContentVec features -- issued
         on a front stream while clip k's synthesizer runs on a back stream.  The two are independent, so the
@@ -376,7 +386,8 @@ class VC(F0Bank):
         timing events (role, group, torch.cuda.Event) at each group's front / back start and end.  ``host_out``
         (a list of pinned host f32 tensors, one per clip, each at least the clip's output length) receives each
         waveform as it is finished: a non-blocking copy on the synthesizer's stream right after that clip,
-        overlapping the next clips' front end (the reference's ``.cpu()`` of each output, convert.py:455)."""
+        overlapping the next clips' front end (the reference's ``.cpu()`` of each output, convert.py:455).
+        ``hop_length`` goes to the f0 methods that read it (``f0_device``)."""
 
         def mark(role, g, stream):
             if events is not None:
@@ -435,11 +446,13 @@ class VC(F0Bank):
                 with torch.cuda.stream(side):
                     side.wait_event(ready)
                     if len(group) == 1:
-                        coarse, pitchf = self.f0_device(xp, pitch, f0_method, xp64=x64s[0])
-                    elif f0_method == "rmvpe":
-                        coarse, pitchf = self._rmvpe().f0_device_batch(xp, 0.03, float(pitch))
+                        coarse, pitchf = self.f0_device(xp, pitch, f0_method, xp64=x64s[0], hop_length=hop_length)
+                    elif f0_method in ("rmvpe", RMVPE_LEGACY):
+                        coarse, pitchf = self._rmvpe().f0_device_batch(xp, 0.03, float(pitch),
+                                                                       f0_range=self._rmvpe_range(f0_method))
                     else:
-                        pairs = [self.f0_device(xp[b], pitch, f0_method, xp64=x64s[b]) for b in range(len(group))]
+                        pairs = [self.f0_device(xp[b], pitch, f0_method, xp64=x64s[b], hop_length=hop_length)
+                                 for b in range(len(group))]
                         coarse, pitchf = torch.stack([c for c, _ in pairs]), torch.stack([f for _, f in pairs])
                     f0_done = torch.cuda.Event()
                     f0_done.record(side)

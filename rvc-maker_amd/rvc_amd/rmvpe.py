@@ -361,13 +361,14 @@ class RMVPEAMD:
         x, Tp = self.mel_image(mel)
         return self.head(self.unet_seq(x, Tp)), Tp
 
-    def decode(self, sal, Tp, F, thred=0.03, pitch_shift=0.0, want_f0=False, post=None):
-        """rmvpe_decode over the first F frames of salience [360][Tp] -> (coarse, pitchf, f0 | None)."""
+    def decode(self, sal, Tp, F, thred=0.03, pitch_shift=0.0, want_f0=False, post=None, f0_range=None):
+        """rmvpe_decode over the first F frames of salience [360][Tp] -> (coarse, pitchf, f0 | None); ``f0_range`` =
+        (f0_min, f0_max) zeroes the decoded f0 outside it before the post steps (rmvpe-legacy, RMVPE.py:228-234)."""
         dev = sal.device
         coarse = torch.empty(F, dtype=torch.int64, device=dev)
         pitchf = torch.empty(F, device=dev)
         f0 = torch.empty(F, dtype=torch.float64, device=dev) if want_f0 else None
-        ops.rmvpe_decode(sal, Tp, F, thred, math.pow(2, pitch_shift / 12), f0, coarse, pitchf, post)
+        ops.rmvpe_decode(sal, Tp, F, thred, math.pow(2, pitch_shift / 12), f0, coarse, pitchf, post, f0_range)
         return coarse, pitchf, f0
 
     @_at_precision
@@ -389,7 +390,7 @@ class RMVPEAMD:
         return self._head(seq, B, Tp), Tp
 
     def f0_device_batch(self, xb: torch.Tensor, thred: float = 0.03, pitch_shift: float = 0.0, post=None,
-                        want_f0=False, want_salience=False):
+                        want_f0=False, want_salience=False, f0_range=None):
         """B equal-length signals [B][N] -> (coarse int64 [B][F], pitchf f32 [B][F]) [+ raw f0 f64 [B][F]]
         [+ salience [B][360][Tp]]; same per-clip result as ``f0_device`` up to the summation order of the batched
         GEMMs (split-K follows the batched grid)."""
@@ -401,18 +402,18 @@ class RMVPEAMD:
         f0 = torch.empty(B, F, dtype=torch.float64, device=xb.device) if want_f0 else None
         for b in range(B):
             ops.rmvpe_decode(sal[b], Tp, F, thred, math.pow(2, pitch_shift / 12), f0[b] if want_f0 else None,
-                             coarse[b], pitchf[b], post)
+                             coarse[b], pitchf[b], post, f0_range)
         out = (coarse, pitchf) + ((f0,) if want_f0 else ()) + ((sal,) if want_salience else ())
         return out
 
     def f0_device(self, audio: torch.Tensor, thred: float = 0.03, pitch_shift: float = 0.0, want_f0=False,
-                  post=None):
+                  post=None, f0_range=None):
         """audio [N] f32 device -> (coarse int64 [F], pitchf f32 [F], f0 f64 [F] | None) on the device;
-        ``post`` (ops.F0Post) adds get_f0's autotune / f0-file steps."""
+        ``post`` (ops.F0Post) adds get_f0's autotune / f0-file steps, ``f0_range`` the legacy range filter (decode)."""
         mel = self.mel_spectrogram(audio)
         F = mel.shape[-1]
         sal, Tp = self.salience(mel)
-        return self.decode(sal, Tp, F, thred, pitch_shift, want_f0, post)
+        return self.decode(sal, Tp, F, thred, pitch_shift, want_f0, post, f0_range)
 
     def check_error(self):
         """Raise if a BiGRU launch since the last check timed out (its f0 is then garbage); clears the flag."""

@@ -1080,6 +1080,38 @@ int rvc_resample_poly64(const void* x, int x_is_f64, int64_t n_in, const double*
                         int64_t n_pre_remove, const int64_t* seg_host, const int64_t* seg_dev, int64_t nseg,
                         double* y64, float* y32, int64_t n_out, rvc_stream_t stream);
 
+/* ------------------------------------------------------------------ training forward and losses
+ * The pieces of the training step's forward (main/inference/train.py:843-866) that the inference path lacks
+ * (trainfwd.hip); the posterior encoder, the flow forward and the decoder are rvc_conv1d launches.  No entry
+ * synchronises or allocates; every pointer is device memory.
+ *
+ * spectrogram: spectrogram_torch (train.py:700-706): B signals x [B][N], reflect-padded by (n_fft - hop) / 2 on both
+ *   sides (which must be < N, and n_fft - hop even), framed every hop with center=False, times win f32 [n_fft] (the
+ *   reference's torch.hann_window(n_fft): win_size == n_fft), an f64 FFT -> spec [B][n_fft / 2 + 1][F] = sqrt(re^2 + im^2 + 1e-6) rounded to f32 once.
+ *   n_fft 1024 or 2048; F = rvc_spectrogram_frames(N, n_fft, hop) (-1: N too short or bad sizes).
+ * mel_log: spec_to_mel_torch (train.py:708-713): mel [B][M][F] = log(max(basis [M][K] @ spec [B][K][F], 1e-5)), one
+ *   launch, the products summed over k in order in f64 and rounded once after the log.
+ * slice_l1: F.l1_loss(slice_segments(mel, ids, S), yhat_mel) (train.py:845, :865): the mean over [B][M][S] of
+ *   |mel [B][M][T] at frames ids[b] + s  -  yhat_mel [B][M][S]|; ids int64 [B] on the device; a start outside
+ *   [0, T - S] reads nothing and gives NaN.
+ * kl_loss: kl_loss (train.py:317-325) at an all-ones mask over z_p, logs_q, m_p, logs_p [B][C][T]: the sum divided
+ *   by B * T.  q_bstride is the batch stride of logs_q, p_bstride that of m_p and logs_p (0: C * T), so the halves
+ *   of stacked [m; logs] statistics pass without a copy.
+ * Both losses: a fixed two-stage sum (RVC_TRAINFWD_RED_BLOCKS partials, then one wave), f64 accumulators, one f32
+ *   result in out[0], no atomics -- bit-identical from run to run.  work: rvc_trainfwd_work_bytes() bytes. */
+enum { RVC_TRAINFWD_RED_BLOCKS = 64 };
+int64_t rvc_spectrogram_frames(int64_t N, int nfft, int hop);
+int rvc_spectrogram(const float* x, const float* win, float* spec, int64_t B, int64_t N, int64_t F, int nfft,
+                    int hop, rvc_stream_t stream);
+int rvc_mel_log(const float* spec, const float* basis, float* mel, int64_t B, int64_t M, int64_t K, int64_t F,
+                rvc_stream_t stream);
+int64_t rvc_trainfwd_work_bytes(void);
+int rvc_slice_l1(const float* mel, const int64_t* ids, const float* yhat_mel, int64_t B, int64_t M, int64_t T, int64_t S,
+                 void* work, int64_t work_bytes, float* out, rvc_stream_t stream);
+int rvc_kl_loss(const float* z_p, const float* logs_q, const float* m_p, const float* logs_p, int64_t B, int64_t C,
+                int64_t T, int64_t q_bstride, int64_t p_bstride, void* work, int64_t work_bytes, float* out,
+                rvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -344,6 +344,14 @@ SIGNATURES = {
     "rvc_peak_mix64": [c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p],
     "rvc_resample_poly64": [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p,
                             c_int64, c_void_p, c_void_p, c_int64, c_void_p],
+    "rvc_spectrogram_frames": [c_int64, c_int, c_int],
+    "rvc_spectrogram": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p],
+    "rvc_mel_log": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p],
+    "rvc_trainfwd_work_bytes": [],
+    "rvc_slice_l1": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                     c_void_p],
+    "rvc_kl_loss": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                    c_int64, c_void_p, c_void_p],
 }
 _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_int64, "rvc_conv1d_x6_bytes": c_int64,
              "rvc_conv64_workspace_bytes": c_int64, "rvc_wino64_workspace_bytes": c_int64,
@@ -363,6 +371,7 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_minibatch_status_bytes": c_int64, "rvc_minibatch_inertia_work_bytes": c_int64,
              "rvc_groupnorm_work_bytes": c_int64, "rvc_fcpe_post_work_bytes": c_int64,
              "rvc_performer_work_bytes": c_int64,
+             "rvc_spectrogram_frames": c_int64, "rvc_trainfwd_work_bytes": c_int64,
              "rvc_lfilter64_warmup": c_int64, "rvc_lfilter64_work_bytes": c_int64, "rvc_frame_rms64_len": c_int64}
 
 _lib = None

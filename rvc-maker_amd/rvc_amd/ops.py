@@ -1269,4 +1269,96 @@ def change_rms(src, src64, out, hop, rate):
     return out
 
 
+# ------------------------------------------------------------------ training forward (trainfwd.hip)
+def spectrogram_frames(N, nfft, hop):
+    """Frames of spectrogram_torch (train.py:700-706) on N samples; ValueError when N does not hold the reflect pad."""
+    F = _lib.load().rvc_spectrogram_frames(N, nfft, hop)
+    if F <= 0:
+        raise ValueError(f"spectrogram: {N} samples do not hold the reflect pad of n_fft {nfft}, hop {hop}")
+    return F
+
+
+_HANN = {}
+
+
+def hann_window(nfft, device):
+    """The reference's window: torch.hann_window(nfft) (periodic, computed in f32 on the host), uploaded once."""
+    key = (nfft, str(device))
+    if key not in _HANN:
+        _HANN[key] = torch.hann_window(nfft, dtype=torch.float32).to(device)
+    return _HANN[key]
+
+
+def spectrogram(x, nfft, hop, out=None):
+    """x [B][N] (or [N]) f32 -> spec [B][nfft/2+1][F] = sqrt(|STFT|^2 + 1e-6) (rvc_spectrogram)."""
+    x2 = x.reshape(1, -1) if x.dim() == 1 else x
+    if x2.dim() != 2 or not x2.is_contiguous():
+        raise ValueError("spectrogram: x must be contiguous [B][N]")
+    win = hann_window(nfft, x.device)
+    B, N = x2.shape
+    F = spectrogram_frames(N, nfft, hop)
+    K = nfft // 2 + 1
+    if out is None:
+        out = torch.empty(B, K, F, device=x.device, dtype=torch.float32)
+    elif out.numel() < B * K * F or not out.is_contiguous():
+        raise ValueError("spectrogram: output buffer too small")
+    check(_lib.load().rvc_spectrogram(_p(x2), _p(win), _p(out), B, N, F, nfft, hop, _stream()), "spectrogram")
+    return out
+
+
+def mel_log(spec, basis, out=None):
+    """spec [B][K][F], basis [M][K] -> log(max(basis @ spec, 1e-5)) [B][M][F] (rvc_mel_log)."""
+    if spec.dim() != 3 or basis.dim() != 2 or not spec.is_contiguous() or not basis.is_contiguous():
+        raise ValueError("mel_log: spec must be contiguous [B][K][F] and basis contiguous [M][K]")
+    B, K, F = spec.shape
+    M = basis.shape[0]
+    if basis.shape[1] != K:
+        raise ValueError(f"mel_log: basis has {basis.shape[1]} bins, spec {K}")
+    if out is None:
+        out = torch.empty(B, M, F, device=spec.device, dtype=torch.float32)
+    elif out.numel() < B * M * F or not out.is_contiguous():
+        raise ValueError("mel_log: output buffer too small")
+    check(_lib.load().rvc_mel_log(_p(spec), _p(basis), _p(out), B, M, K, F, _stream()), "mel_log")
+    return out
+
+
+def _loss_work(device):
+    n = _lib.load().rvc_trainfwd_work_bytes()
+    return torch.empty(n // 4, device=device, dtype=torch.float32), n
+
+
+def slice_l1(mel, ids, yhat_mel):
+    """F.l1_loss(slice_segments(mel, ids, S), yhat_mel): mel [B][M][T], ids int64 [B] (device), yhat_mel [B][M][S] ->
+    a device f32 scalar [1] (rvc_slice_l1: fixed-order f64 sum)."""
+    if mel.dim() != 3 or yhat_mel.dim() != 3 or not mel.is_contiguous() or not yhat_mel.is_contiguous():
+        raise ValueError("slice_l1: mel [B][M][T] and yhat_mel [B][M][S] must be contiguous")
+    B, M, T = mel.shape
+    S = yhat_mel.shape[2]
+    if yhat_mel.shape[:2] != (B, M) or S > T or ids.dtype != torch.int64 or ids.numel() != B:
+        raise ValueError("slice_l1: shape mismatch")
+    work, nb = _loss_work(mel.device)
+    out = torch.empty(1, device=mel.device, dtype=torch.float32)
+    check(_lib.load().rvc_slice_l1(_p(mel), _p(ids), _p(yhat_mel), B, M, T, S, _p(work), nb, _p(out), _stream()),
+          "slice_l1")
+    return out
+
+
+def kl_loss(z_p, logs_q, m_p, logs_p):
+    """kl_loss(z_p, logs_q, m_p, logs_p, ones) (train.py:317-325) over [B][C][T] -> a device f32 scalar [1].  m_p and
+    logs_p may be the two halves of stacked statistics [B][2C][T] (views with batch stride 2 * C * T)."""
+    B, C, T = z_p.shape
+    for t in (logs_q, m_p, logs_p):
+        if tuple(t.shape) != (B, C, T) or t.stride(2) != 1 or t.stride(1) != T:
+            raise ValueError("kl_loss: operands must be [B][C][T] with contiguous rows")
+    if not z_p.is_contiguous() or m_p.stride(0) != logs_p.stride(0):
+        raise ValueError("kl_loss: z_p must be contiguous, m_p and logs_p share a batch stride")
+    work, nb = _loss_work(z_p.device)
+    out = torch.empty(1, device=z_p.device, dtype=torch.float32)
+    qs = logs_q.stride(0) if B > 1 else 0
+    ps = m_p.stride(0) if B > 1 else 0
+    check(_lib.load().rvc_kl_loss(_p(z_p), _p(logs_q), _p(m_p), _p(logs_p), B, C, T, qs, ps, _p(work), nb, _p(out),
+                                  _stream()), "kl_loss")
+    return out
+
+
 SQRT = math.sqrt

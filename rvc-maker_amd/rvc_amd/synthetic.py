@@ -234,8 +234,104 @@ def make_synth_ckpt(sr: int = 48000, version: str = "v2", seed: int = 1234, voco
     return opt
 
 
+# ---------------------------------------------------------------- training checkpoints (G_*.pth)
+# main/configs/v{1,2}/*.json: "train".segment_size and the "data" section's mel settings, per sample rate
+_TRAIN_TABLE = {
+    32000: dict(hop_length=320, n_mel_channels=80, segment_size=dict(v1=12800, v2=12800)),
+    40000: dict(hop_length=400, n_mel_channels=125, segment_size=dict(v1=12800, v2=12800)),
+    48000: dict(hop_length=480, n_mel_channels=128, segment_size=dict(v1=11520, v2=17280)),
+}
+ENC_Q_LAYERS, ENC_Q_KERNEL = 16, 5  # PosteriorEncoder(spec_channels, inter, hidden, 5, 1, 16) (synthesizers.py:424)
+
+
+def train_config(sr: int = 40000, version: str = "v2", spk_embed_dim: int = 109) -> dict:
+    """The experiment folder's ``config.json`` (main/configs/v{1,2}/{sr}.json) as a dict."""
+    t, d = _SR_TABLE[sr], _TRAIN_TABLE[sr]
+    v = t[version]
+    return {
+        "train": {"log_interval": 200, "seed": 1234, "learning_rate": 1e-4, "betas": [0.8, 0.99], "eps": 1e-9,
+                  "lr_decay": 0.999875, "segment_size": d["segment_size"][version], "c_mel": 45, "c_kl": 1.0},
+        "data": {"max_wav_value": 32768.0, "sample_rate": sr, "filter_length": t["filter_length"],
+                 "hop_length": d["hop_length"], "win_length": t["filter_length"],
+                 "n_mel_channels": d["n_mel_channels"], "mel_fmin": 0.0, "mel_fmax": None},
+        "model": {"inter_channels": 192, "hidden_channels": 192, "filter_channels": 768,
+                  "text_enc_hidden_dim": 768 if version == "v2" else 256, "n_heads": 2, "n_layers": 6,
+                  "kernel_size": 3, "p_dropout": 0, "resblock": "1", "resblock_kernel_sizes": [3, 7, 11],
+                  "resblock_dilation_sizes": [[1, 3, 5], [1, 3, 5], [1, 3, 5]],
+                  "upsample_rates": list(v["upsample_rates"]), "upsample_initial_channel": 512,
+                  "upsample_kernel_sizes": list(v["upsample_kernel_sizes"]), "use_spectral_norm": False,
+                  "gin_channels": 256, "spk_embed_dim": spk_embed_dim},
+    }
+
+
+def enc_q_state_dict(cfg: list, seed: int = 1234) -> "OrderedDict[str, torch.Tensor]":
+    """fp32 state dict of ``Synthesizer.enc_q`` (PosteriorEncoder, synthesizers.py:373-391; WaveNet, modules.py:9-33)
+    in the checkpoint's key layout (``.weight_g`` / ``.weight_v``), from a generator of its own: the other
+    functions' draws do not move.  The 1x1 ``pre`` conv sees linear magnitudes (peaks of 10^2), so its gain is small
+    enough that the gates are not all saturated."""
+    spec_channels, inter, hidden, gin = cfg[0], cfg[2], cfg[3], cfg[16]
+    g = _Gen(seed ^ 0x51C0DE)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    _conv(g, sd, "enc_q.pre", hidden, spec_channels, 1, gain=0.15)
+    for l in range(ENC_Q_LAYERS):
+        sd[f"enc_q.enc.in_layers.{l}.bias"] = g.normal((2 * hidden,), 0.02)
+        _wn(g, sd, f"enc_q.enc.in_layers.{l}", (2 * hidden, hidden, ENC_Q_KERNEL),
+            1.0 / math.sqrt(hidden * ENC_Q_KERNEL))
+    for l in range(ENC_Q_LAYERS):
+        rs = hidden if l == ENC_Q_LAYERS - 1 else 2 * hidden
+        sd[f"enc_q.enc.res_skip_layers.{l}.bias"] = g.normal((rs,), 0.02)
+        _wn(g, sd, f"enc_q.enc.res_skip_layers.{l}", (rs, hidden, 1), 0.5 / math.sqrt(hidden))
+    sd["enc_q.enc.cond_layer.bias"] = g.normal((2 * hidden * ENC_Q_LAYERS,), 0.02)
+    _wn(g, sd, "enc_q.enc.cond_layer", (2 * hidden * ENC_Q_LAYERS, gin, 1), 0.5 / math.sqrt(gin))
+    _conv(g, sd, "enc_q.proj", inter * 2, hidden, 1, gain=0.25)
+    return sd
+
+
+def make_train_ckpt(sr: int = 40000, version: str = "v2", seed: int = 1234) -> dict:
+    """A generator training checkpoint ``G_*.pth`` as ``save_checkpoint`` writes it (train.py:269-271): fp32
+    ``{"model": Synthesizer.state_dict() with .weight_g / .weight_v, "iteration", "optimizer", "learning_rate"}``
+    -- ``synth_state_dict`` plus ``enc_q_state_dict``."""
+    cfg = synth_config(sr, version)
+    sd = synth_state_dict(cfg, seed, emb_dim=768 if version == "v2" else 256)
+    sd.update(enc_q_state_dict(cfg, seed))
+    return {"model": sd, "iteration": 1, "optimizer": {}, "learning_rate": 1e-4}
+
+
+def write_train_experiment(exp_dir: str, sr: int = 40000, version: str = "v2", frames=(150, 150), seed: int = 1234,
+                           sid: int = 3) -> str:
+    """A seeded experiment folder as the reference's preprocessing and extraction leave it: ``config.json``,
+    ``filelist.txt`` (``wav|phone.npy|pitch.npy|pitchf.npy|sid``), per utterance an IEEE-float wav of
+    ``frames[i] * hop`` samples, features of ``frames[i] // 2`` rows (the loader repeats them x2), pitch and pitchf
+    of ``frames[i]`` rows with about a quarter unvoiced -- and ``G_1.pth`` (``make_train_ckpt``), whose path is
+    returned."""
+    import json
+    import os
+    from . import audio_io
+    hps = train_config(sr, version)
+    hop, emb = hps["data"]["hop_length"], 768 if version == "v2" else 256
+    os.makedirs(exp_dir, exist_ok=True)
+    with open(os.path.join(exp_dir, "config.json"), "w", encoding="utf-8") as f:
+        json.dump(hps, f, indent=1)
+    rows = []
+    for i, T in enumerate(frames):
+        rng = np.random.Generator(np.random.PCG64(seed + 100 + i))
+        stem = os.path.join(exp_dir, f"utt{i}")
+        audio_io.write_wav_f32(stem + ".wav", synthetic_audio(T * hop / sr + 0.01, seed=seed + i, sr=sr)[:T * hop], sr)
+        np.save(stem + "_phone.npy", rng.standard_normal((T // 2, emb)).astype(np.float32))
+        np.save(stem + "_pitch.npy", rng.integers(1, 256, size=T).astype(np.int64))
+        pitchf = rng.uniform(60, 500, size=T).astype(np.float32)
+        pitchf[rng.random(T) < 0.25] = 0.0
+        np.save(stem + "_pitchf.npy", pitchf)
+        rows.append(f"{stem}.wav|{stem}_phone.npy|{stem}_pitch.npy|{stem}_pitchf.npy|{sid}")
+    with open(os.path.join(exp_dir, "filelist.txt"), "w", encoding="utf-8") as f:
+        f.write("\n".join(rows) + "\n")
+    path = os.path.join(exp_dir, "G_1.pth")
+    torch.save(make_train_ckpt(sr, version, seed), path)
+    return path
+
+
 # ---------------------------------------------------------------- ContentVec
-HUBERT_CFG = dict(_name="hubert", label_rate=50, encoder_layers_1=3, logit_temp_ctr=0.1, num_negatives=100,
+HUBERT_CFG =dict(_name="hubert", label_rate=50, encoder_layers_1=3, logit_temp_ctr=0.1, num_negatives=100,
                   cross_sample_negatives=0, ctr_layers=[-6], extractor_mode="default", encoder_layers=12,
                   encoder_embed_dim=768, encoder_ffn_embed_dim=3072, encoder_attention_heads=12,
                   activation_fn="gelu", layer_type="transformer", dropout=0.1, attention_dropout=0.1,

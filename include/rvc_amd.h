@@ -1112,6 +1112,37 @@ int rvc_kl_loss(const float* z_p, const float* logs_q, const float* m_p, const f
                 int64_t T, int64_t q_bstride, int64_t p_bstride, void* work, int64_t work_bytes, float* out,
                 rvc_stream_t stream);
 
+/* ---- the discriminators' own kernels and the GAN losses (csrc/discriminator.hip; train.py:608-674, 286-315)
+ * period_front: DiscriminatorP.forward up to its first feature map, for S signals y [S][t]: the right reflect pad
+ *   (p - t % p) % p (which must be < t), the [H][p] view, Conv2d(1, 32, (5,1), (3,1), padding=(2,0)) with w [32][5] and
+ *   bias [32], LeakyReLU(slope) -> out [S * p][32][H1]: column c of signal s is batch element s * p + c, so every later
+ *   (k,1) Conv2d is a batched Conv1d over H.  H1 = rvc_period_front_rows(t, p) (-1: the pad does not fit).
+ * gconv_small: Conv1d(Ci, Co, 41, 4, groups = Ci / 4, padding = 20) + bias + LeakyReLU(slope) as a direct f32 kernel:
+ *   x [B][Ci][Lin], w [Co][4][41], y [B][Co][Lout], Lout = (Lin - 1) / 4 + 1; Co / groups is 16 or 4.
+ * pair_l1: table[slot] = mean |a[i] - b[i]| over n values.  lsgan_terms: table[slot .. slot + 2] = mean (1 - d_r)^2,
+ *   mean d_g^2, mean (1 - d_g)^2 over n values each.  Both are the fixed two-stage f64 sum of slice_l1, kept in f64;
+ *   work: rvc_disc_work_bytes() bytes, reused by calls on one stream.
+ * disc_finish: table = n_fm feature-map terms in the reference's list order, then (r, g, gen) per discriminator
+ *   (rvc_disc_table_slots(n_fm, n_disc) doubles).  Each term is rounded to f32 and added in f32 in list order, as the
+ *   reference's Python sums do: out[0] = loss_disc, [1] = loss_gen, [2] = loss_fm = 2 * sum, and -- with the device
+ *   scalars l1 and kl (rvc_slice_l1 / rvc_kl_loss; both or neither) -- [4] = loss_mel = l1 * c_mel, [5] = loss_kl =
+ *   kl * c_kl, [3] = loss_gen_all = loss_gen + loss_fm + loss_mel + loss_kl (NaN without them); from
+ *   out[RVC_DISC_OUT_LISTS]: losses_gen [n_disc], losses_disc_r [n_disc], losses_disc_g [n_disc]. */
+enum { RVC_DISC_OUT_LISTS = 6 };
+int64_t rvc_period_front_rows(int64_t t, int p);
+int rvc_period_front(const float* y, const float* w, const float* bias, float* out, int64_t S, int64_t t, int p,
+                     int64_t H1, float slope, rvc_stream_t stream);
+int rvc_gconv_small(const float* x, const float* w, const float* bias, float* y, int64_t B, int64_t Ci, int64_t Co,
+                    int64_t Lin, int64_t Lout, float slope, rvc_stream_t stream);
+int64_t rvc_disc_work_bytes(void);
+int64_t rvc_disc_table_slots(int n_fm, int n_disc);
+int rvc_pair_l1(const float* a, const float* b, int64_t n, double* table, int64_t slot, void* work, int64_t work_bytes,
+                rvc_stream_t stream);
+int rvc_lsgan_terms(const float* d_r, const float* d_g, int64_t n, double* table, int64_t slot, void* work,
+                    int64_t work_bytes, rvc_stream_t stream);
+int rvc_disc_finish(const double* table, int n_fm, int n_disc, const float* l1, float c_mel, const float* kl, float c_kl,
+                    float* out, rvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,17 +3,11 @@
 // discriminator-free generator losses -- F.l1_loss on the sliced mel (:845, :865) and kl_loss (:317-325).
 // The posterior encoder, the flow forward and the decoder run on the conv engine (rvc_amd/train_forward.py).
 #include "fft_lds.h"
+#include "reduce64.h"
 
 namespace {
 
-constexpr int RED_BLOCKS = RVC_TRAINFWD_RED_BLOCKS;  // stage-1 blocks of both reductions
 constexpr int MEL_ROWS = 4;                          // basis rows per thread of mel_log_kernel
-
-RVC_DEV double wave_sum64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ------------------------------------------------------------------ spectrogram (train.py:700-706)
 // One block per (frame, signal): the reflect-padded frame times the window (the reference's f32 torch.hann_window,
@@ -68,23 +62,8 @@ __global__ __launch_bounds__(64) void mel_log_kernel(const float* __restrict__ s
 }
 
 // ------------------------------------------------------------------ the two losses: fixed two-stage sums
-// Stage 1: RED_BLOCKS blocks, block i over the i-th contiguous chunk of the n terms; a thread adds its terms in index
-// order, the wave by the xor tree, the four waves in one written order -> part[i].  Stage 2: one wave adds the
-// RED_BLOCKS partials by the same tree and divides.  f64 throughout, one rounding to f32; no atomics, so two runs give
-// the same bits.
-template <typename Term>
-RVC_DEV void reduce_stage1(int64_t n, double* __restrict__ part, Term term) {
-    __shared__ double ws[4];
-    const int64_t len = (n + RED_BLOCKS - 1) / RED_BLOCKS;
-    const int64_t i0 = blockIdx.x * len, i1 = i0 + len < n ? i0 + len : n;
-    double s = 0.0;
-    for (int64_t i = i0 + threadIdx.x; i < i1; i += blockDim.x) s += term(i);
-    s = wave_sum64(s);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
-}
-
+// reduce64.h's stage 1 over the n terms, then one wave adds the RED_BLOCKS partials by the same tree and divides.  f64
+// throughout, one rounding to f32; no atomics, so two runs give the same bits.
 __global__ __launch_bounds__(64) void reduce_stage2(const double* __restrict__ part, double denom,
                                                     float* __restrict__ out) {
     static_assert(RED_BLOCKS == 64, "stage 2 is one wave over the partials");

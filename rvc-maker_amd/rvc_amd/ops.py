@@ -1361,4 +1361,112 @@ def kl_loss(z_p, logs_q, m_p, logs_p):
     return out
 
 
+# ------------------------------------------------------------------ discriminators and GAN losses (discriminator.hip)
+def period_front_rows(t, p):
+    """Rows H1 of DiscriminatorP's first feature map on t samples; ValueError when the reflect pad does not fit."""
+    H1 = _lib.load().rvc_period_front_rows(t, p)
+    if H1 <= 0:
+        raise ValueError(f"period_front: {t} samples do not hold the reflect pad of period {p}")
+    return H1
+
+
+def period_front(y, w, bias, p, slope=0.1, out=None):
+    """y [S][t] (or [t]) -> [S * p][32][H1]: reflect pad, [H][p] view, Conv2d(1, 32, (5,1), (3,1), (2,0)) with w [32][5]
+    and bias [32], LeakyReLU -- column c of signal s is batch element s * p + c (rvc_period_front)."""
+    y2 = y.reshape(1, -1) if y.dim() == 1 else y
+    if y2.dim() != 2 or not y2.is_contiguous():
+        raise ValueError("period_front: y must be contiguous [S][t]")
+    if w.numel() != 32 * 5 or bias.numel() != 32 or not w.is_contiguous():
+        raise ValueError("period_front: w must be [32][5] and bias [32]")
+    S, t = y2.shape
+    H1 = period_front_rows(t, p)
+    if out is None:
+        out = torch.empty(S * p, 32, H1, device=y.device, dtype=torch.float32)
+    elif out.numel() < S * p * 32 * H1 or not out.is_contiguous():
+        raise ValueError("period_front: output buffer too small")
+    check(_lib.load().rvc_period_front(_p(y2), _p(w), _p(bias), _p(out), S, t, p, H1, slope, _stream()),
+          "period_front")
+    return out
+
+
+def gconv_small(x, w, bias, slope=0.1, out=None):
+    """Conv1d(Ci, Co, 41, 4, groups=Ci / 4, padding=20) + bias + LeakyReLU: x [B][Ci][Lin], w [Co][4][41] ->
+    [B][Co][(Lin - 1) // 4 + 1] (rvc_gconv_small)."""
+    if x.dim() != 3 or not x.is_contiguous() or w.dim() != 3 or not w.is_contiguous():
+        raise ValueError("gconv_small: x must be contiguous [B][Ci][Lin] and w contiguous [Co][4][41]")
+    B, Ci, Lin = x.shape
+    Co = w.shape[0]
+    if tuple(w.shape[1:]) != (4, 41) or Ci % 4 or Co * 4 not in (16 * Ci, 4 * Ci) or bias.numel() != Co:
+        raise ValueError(f"gconv_small: {Ci} -> {Co} channels with weight {tuple(w.shape)} is not one of its layers")
+    Lout = (Lin - 1) // 4 + 1
+    if out is None:
+        out = torch.empty(B, Co, Lout, device=x.device, dtype=torch.float32)
+    elif out.numel() < B * Co * Lout or not out.is_contiguous():
+        raise ValueError("gconv_small: output buffer too small")
+    check(_lib.load().rvc_gconv_small(_p(x), _p(w), _p(bias), _p(out), B, Ci, Co, Lin, Lout, slope, _stream()),
+          "gconv_small")
+    return out
+
+
+def _pd64(t):
+    if not t.is_cuda or t.dtype != torch.float64:
+        raise TypeError(f"rvc_amd: expected a CUDA f64 tensor, got {t.dtype} on {t.device}")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def disc_work(device):
+    """The reductions' stage-1 scratch (rvc_disc_work_bytes) -> (f64 buffer, bytes); calls on one stream may share it."""
+    n = _lib.load().rvc_disc_work_bytes()
+    return torch.empty(n // 8, device=device, dtype=torch.float64), n
+
+
+def disc_table(n_fm, n_disc, device):
+    """The f64 table rvc_disc_finish sums: n_fm feature-map terms, then (r, g, gen) per discriminator."""
+    return torch.zeros(_lib.load().rvc_disc_table_slots(n_fm, n_disc), device=device, dtype=torch.float64)
+
+
+def _flat_pair(a, b, what):
+    if a.numel() != b.numel() or a.numel() == 0 or not a.is_contiguous() or not b.is_contiguous():
+        raise ValueError(f"{what}: two contiguous tensors of one size, not {tuple(a.shape)} and {tuple(b.shape)}")
+    return a.numel()
+
+
+def pair_l1(a, b, table, slot, work=None):
+    """table[slot] = mean |a - b| (rvc_pair_l1: fixed-order f64 sum)."""
+    n = _flat_pair(a, b, "pair_l1")
+    if not 0 <= slot < table.numel():
+        raise ValueError(f"pair_l1: slot {slot} outside a table of {table.numel()}")
+    work, nb = (work, work.numel() * 8) if work is not None else disc_work(a.device)
+    check(_lib.load().rvc_pair_l1(_p(a), _p(b), n, _pd64(table), slot, _pd64(work), nb, _stream()), "pair_l1")
+    return table
+
+
+def lsgan_terms(d_r, d_g, table, slot, work=None):
+    """table[slot : slot + 3] = mean (1 - d_r)^2, mean d_g^2, mean (1 - d_g)^2 (rvc_lsgan_terms)."""
+    n = _flat_pair(d_r, d_g, "lsgan_terms")
+    if not 0 <= slot <= table.numel() - 3:
+        raise ValueError(f"lsgan_terms: slots {slot}..{slot + 2} outside a table of {table.numel()}")
+    work, nb = (work, work.numel() * 8) if work is not None else disc_work(d_r.device)
+    check(_lib.load().rvc_lsgan_terms(_p(d_r), _p(d_g), n, _pd64(table), slot, _pd64(work), nb, _stream()),
+          "lsgan_terms")
+    return table
+
+
+DISC_OUT_LISTS = 6  # RVC_DISC_OUT_LISTS
+
+
+def disc_finish(table, n_fm, n_disc, l1=None, c_mel=1.0, kl=None, c_kl=1.0):
+    """The reference's f32 sums over the table -> device f32 [6 + 3 * n_disc]: loss_disc, loss_gen, loss_fm,
+    loss_gen_all, loss_mel, loss_kl (the last three NaN without the device scalars ``l1`` and ``kl``), then losses_gen,
+    losses_disc_r, losses_disc_g (rvc_disc_finish)."""
+    if table.numel() < n_fm + 3 * n_disc:
+        raise ValueError("disc_finish: table too small")
+    if (l1 is None) != (kl is None):
+        raise ValueError("disc_finish: loss_mel and loss_kl go together")
+    out = torch.empty(DISC_OUT_LISTS + 3 * n_disc, device=table.device, dtype=torch.float32)
+    check(_lib.load().rvc_disc_finish(_pd64(table), n_fm, n_disc, _p(l1), c_mel, _p(kl), c_kl, _p(out), _stream()),
+          "disc_finish")
+    return out
+
+
 SQRT = math.sqrt

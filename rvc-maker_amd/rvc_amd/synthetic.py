@@ -297,13 +297,39 @@ def make_train_ckpt(sr: int = 40000, version: str = "v2", seed: int = 1234) -> d
     return {"model": sd, "iteration": 1, "optimizer": {}, "learning_rate": 1e-4}
 
 
+def discriminator_state_dict(version: str = "v2", seed: int = 1234) -> "OrderedDict[str, torch.Tensor]":
+    """fp32 state dict of ``MultiPeriodDiscriminator(version)`` (train.py:608-674) in the checkpoint's key layout, from
+    a generator of its own.  ``weight_v ~ N(0, std)`` with ``std = gain / sqrt(fan_in)``; ``weight_g`` is drawn as
+    ``std * sqrt(fan_in) * U(0.7, 1.3)`` -- the expected norm of v times the usual spread, never a computed norm,
+    whose f32 summation order differs between hosts: these 71 M parameters regenerate bit for bit from the seed.
+    Gains keep the activations O(1) through the six layers: a LeakyReLU(0.1) passes about half the power, so sqrt(2)
+    holds a layer's RMS; the first conv of each discriminator sees audio at an RMS of 0.1-0.2 and takes 6."""
+    from .discriminator import discriminator_layers
+    g = _Gen(seed ^ 0xD15C)
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for name, shape, _ in discriminator_layers(version):
+        fan_in = int(np.prod(shape[1:]))
+        gain = 6.0 if name.endswith("convs.0") else 1.0 if name.endswith("conv_post") else math.sqrt(2.0)
+        std = gain / math.sqrt(fan_in)
+        sd[name + ".bias"] = g.normal((shape[0],), 0.02)
+        # std * sqrt(fan_in) is the gain; an elementwise f32 product, the same on every host
+        sd[name + ".weight_g"] = g.uniform((shape[0],) + (1,) * (len(shape) - 1), 0.7, 1.3) * float(gain)
+        sd[name + ".weight_v"] = g.normal(shape, std)
+    return sd
+
+
+def make_disc_ckpt(version: str = "v2", seed: int = 1234) -> dict:
+    """A discriminator training checkpoint ``D_*.pth`` as ``save_checkpoint`` writes it (train.py:269-271)."""
+    return {"model": discriminator_state_dict(version, seed), "iteration": 1, "optimizer": {}, "learning_rate": 1e-4}
+
+
 def write_train_experiment(exp_dir: str, sr: int = 40000, version: str = "v2", frames=(150, 150), seed: int = 1234,
-                           sid: int = 3) -> str:
+                           sid: int = 3, with_d: bool = False) -> str:
     """A seeded experiment folder as the reference's preprocessing and extraction leave it: ``config.json``,
     ``filelist.txt`` (``wav|phone.npy|pitch.npy|pitchf.npy|sid``), per utterance an IEEE-float wav of
     ``frames[i] * hop`` samples, features of ``frames[i] // 2`` rows (the loader repeats them x2), pitch and pitchf
     of ``frames[i]`` rows with about a quarter unvoiced -- and ``G_1.pth`` (``make_train_ckpt``), whose path is
-    returned."""
+    returned.  ``with_d`` also writes ``D_1.pth`` (``make_disc_ckpt``) beside it."""
     import json
     import os
     from . import audio_io
@@ -327,6 +353,8 @@ def write_train_experiment(exp_dir: str, sr: int = 40000, version: str = "v2", f
         f.write("\n".join(rows) + "\n")
     path = os.path.join(exp_dir, "G_1.pth")
     torch.save(make_train_ckpt(sr, version, seed), path)
+    if with_d:
+        torch.save(make_disc_ckpt(version, seed), os.path.join(exp_dir, "D_1.pth"))
     return path
 
 

@@ -1,19 +1,24 @@
-"""The training step's forward and its two discriminator-free losses on the MI355X (main/inference/train.py).
+"""The training step's forward and its losses on the MI355X (main/inference/train.py).
 
 What runs here is ``net_g(...)`` of ``train.py:843`` -- ``Synthesizer.forward`` (synthesizers.py:434-442): the prior
 encoder, the posterior encoder ``enc_q`` and its sample, the random segment slice, the NSF decoder on the slice, the
 flow in the forward direction -- plus the linear and mel spectrograms (``train.py:700-716``) and ``loss_mel`` /
-``loss_kl`` as the training loop logs them (``train.py:844-848, 865-866``).  On top of that:
+``loss_kl`` as the training loop logs them (``train.py:844-848, 865-866``).  With a ``D_*.pth`` beside the ``G_*.pth``
+(``rvc_amd.discriminator``), also ``net_d`` on the wave slice and ``y_hat`` and the GAN losses ``loss_disc``,
+``loss_gen``, ``loss_fm`` and ``loss_gen_all`` (``train.py:850-869``): the number the reference keeps its
+``lowest_value`` on and the two series its overtraining detector smooths.  On top of that:
 
-* ``evaluate``         scores a ``G_*.pth`` on an experiment folder's filelist (which checkpoint is best, is it
-                       overtraining) -- ``python -m rvc_amd.train_forward --exp DIR --ckpt G_123.pth``;
+* ``evaluate``         scores a ``G_*.pth``, or a (G, D) pair, on an experiment folder's filelist (which checkpoint is
+                       best, is it overtraining) --
+                       ``python -m rvc_amd.train_forward --exp DIR --ckpt G_123.pth [--d-ckpt D_123.pth]``;
 * ``write_spec_cache`` writes the ``*.spec.pt`` files the reference's loader otherwise computes on the CPU in its
                        first epoch (``train.py:377-393``).
 
 One utterance per call (B = 1, no padding): every mask of the reference is all ones, and its padded batch computes
-the same values on an utterance's valid frames.  No backward pass, no discriminators, no AMP; the
-MRF-HiFi-GAN and RefineGAN decoders are refused here.  The kernels are csrc/trainfwd.hip; the encoder, flow and decoder
-run on the conv engine as ``SynthesizerAMD`` does.
+the same values on an utterance's valid frames.  No backward pass, no optimizer step (so both of the
+loop's ``net_d`` passes see the saved D), no AMP; the MRF-HiFi-GAN and RefineGAN decoders are refused
+here.  The kernels are csrc/trainfwd.hip and csrc/discriminator.hip; the encoder, flow, decoder and most of the
+discriminators' layers run on the conv engine as ``SynthesizerAMD`` does.
 """
 from __future__ import annotations
 
@@ -269,6 +274,37 @@ def generator_losses(model: TrainSynthAMD, phone, pitch, pitchf, spec, sid, cfg:
             "loss_kl": float(both[1] * np.float32(hps["train"]["c_kl"]))}
 
 
+D_LOSSES = ("loss_disc", "loss_gen", "loss_fm")  # the new per-utterance scalars, each aggregated as a plain mean
+
+
+def step_losses(model: TrainSynthAMD, disc, phone, pitch, pitchf, spec, wave, sid, cfg: dict = None, **draws) -> dict:
+    """Every loss of one training step on one utterance (train.py:843-869): the forward, ``wave`` [T * hop] sliced at
+    ``ids_slice * hop`` for ``segment_size`` samples (train.py:850), ``disc`` (a ``DiscriminatorAMD``) on that slice
+    and ``y_hat`` -> ``DiscriminatorAMD.losses``' dict with ``loss_mel``, ``loss_kl`` and ``loss_gen_all`` (floats, one
+    host read).  ``loss_mel`` and ``loss_kl`` are the bits ``generator_losses`` returns for the same draws."""
+    hps = cfg or model.hps
+    y_hat, ids, (z, z_p, m_p, logs_p, m_q, logs_q) = model.forward(phone, pitch, pitchf, spec, sid, **draws)
+    l1, kl = _losses(hps, spec, y_hat, ids, z_p, logs_q, m_p, logs_p)
+    seg, st = y_hat.numel(), int(ids.item()) * model.hop
+    wave = wave.reshape(-1)
+    if st + seg > wave.numel():
+        raise ValueError(f"step_losses: the wave has {wave.numel()} samples, the slice ends at {st + seg}")
+    return disc.losses(wave[st:st + seg].float().contiguous(), y_hat, l1, kl, float(hps["train"]["c_mel"]),
+                       float(hps["train"]["c_kl"]))
+
+
+def aggregate_gan(per_utt: list) -> dict:
+    """The new losses over utterances: each the plain mean (every slice has ``segment_size`` samples, so a batch's
+    means are the means of the utterances' means), and ``loss_gen_all`` the sum of the four aggregates (train.py:869).
+    per_utt: ``aggregate``'s dicts with ``loss_disc``, ``loss_gen`` and ``loss_fm`` added."""
+    if not per_utt:
+        return {k: None for k in D_LOSSES + ("loss_gen_all",)}
+    out = {k: sum(u[k] for u in per_utt) / len(per_utt) for k in D_LOSSES}
+    base = aggregate(per_utt)
+    out["loss_gen_all"] = out["loss_gen"] + out["loss_fm"] + base["loss_mel"] + base["loss_kl"]
+    return out
+
+
 # ---------------------------------------------------------------------- experiment folders
 def read_filelist(path: str) -> list:
     """filelist.txt rows ``wav|phone.npy|pitch.npy|pitchf.npy|sid`` (train.py:282-284, 342)."""
@@ -351,12 +387,22 @@ def write_spec_cache(exp_dir: str, device: str = "cuda") -> dict:
     return {"written": written, "skipped": skipped}
 
 
+def _wave_of(wav_path, device):
+    from . import audio_io
+    x, _ = audio_io.read_wav(wav_path)
+    return torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(device)
+
+
 def evaluate(exp_dir: str, checkpoint, limit: int = None, seed: int = 0, device: str = "cuda",
-             vocoder: str = "Default") -> dict:
+             vocoder: str = "Default", d_checkpoint=None) -> dict:
     """Score a generator checkpoint (a ``G_*.pth`` path, its loaded dict, or a built ``TrainSynthAMD``) on the
     utterances of ``exp_dir/filelist.txt``: per-utterance ``loss_mel`` / ``loss_kl`` and the aggregates one reference
     batch of them would log (``aggregate``).  Utterance i of the filelist draws from ``seed + i``, so its numbers do
-    not depend on ``limit`` or on the others; utterances shorter than the training segment are skipped and counted."""
+    not depend on ``limit`` or on the others; utterances shorter than the training segment are skipped and counted.
+
+    ``d_checkpoint`` (a ``D_*.pth`` path, its loaded dict, or a built ``DiscriminatorAMD``): the entries and the
+    aggregates also carry ``loss_disc``, ``loss_gen``, ``loss_fm`` and ``loss_gen_all`` (``step_losses``,
+    ``aggregate_gan``), the entries the per-discriminator lists too.  Without it the result is what it always was."""
     hps = _load_hps(exp_dir)
     if isinstance(checkpoint, TrainSynthAMD):
         model = checkpoint
@@ -364,6 +410,13 @@ def evaluate(exp_dir: str, checkpoint, limit: int = None, seed: int = 0, device:
         ck = torch.load(checkpoint, map_location="cpu", weights_only=False) if isinstance(checkpoint, str) \
             else checkpoint
         model = TrainSynthAMD(ck, hps, device, vocoder=vocoder)
+    disc = None
+    if d_checkpoint is not None:
+        from .discriminator import DiscriminatorAMD
+        disc = d_checkpoint
+        if not isinstance(disc, DiscriminatorAMD):
+            dk = torch.load(disc, map_location="cpu", weights_only=False) if isinstance(disc, str) else disc
+            disc = DiscriminatorAMD(dk, model.version, device)
     rows = read_filelist(os.path.join(exp_dir, "filelist.txt"))
     if limit is not None:
         rows = rows[:limit]
@@ -375,29 +428,43 @@ def evaluate(exp_dir: str, checkpoint, limit: int = None, seed: int = 0, device:
         if T < S:
             skipped += 1
             continue
-        losses = generator_losses(model, torch.from_numpy(phone.astype(np.float32)).to(device),
-                                  torch.from_numpy(pitch.astype(np.int64)).to(device),
-                                  torch.from_numpy(pitchf.astype(np.float32)).to(device),
-                                  spec[:, :T].contiguous(), parse_sid(sid), hps, seed=seed + i)
+        args = (torch.from_numpy(phone.astype(np.float32)).to(device),
+                torch.from_numpy(pitch.astype(np.int64)).to(device),
+                torch.from_numpy(pitchf.astype(np.float32)).to(device), spec[:, :T].contiguous())
+        if disc is None:
+            losses = generator_losses(model, *args, parse_sid(sid), hps, seed=seed + i)
+        else:
+            losses = step_losses(model, disc, *args, _wave_of(wav, device), parse_sid(sid), hps, seed=seed + i)
         per_utt.append({"index": i, "wav": wav, "frames": T, **losses})
     out = aggregate(per_utt)
+    if disc is not None:
+        out.update(aggregate_gan(per_utt))
     out.update(utterances=per_utt, scored=len(per_utt), skipped=skipped)
     return out
 
 
 def main(argv=None):
     import argparse
-    ap = argparse.ArgumentParser(description="loss_mel / loss_kl of generator checkpoints on an experiment folder")
+    ap = argparse.ArgumentParser(description="loss_mel / loss_kl of generator checkpoints on an experiment folder; "
+                                             "with their D_*.pth also loss_disc / loss_gen / loss_fm / loss_gen_all")
     ap.add_argument("--exp", required=True, help="experiment folder (config.json, filelist.txt)")
     ap.add_argument("--ckpt", required=True, action="append", help="G_*.pth (repeatable)")
+    ap.add_argument("--d-ckpt", action="append", default=None,
+                    help="D_*.pth, once per --ckpt and paired with them in order")
     ap.add_argument("--limit", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda")
     a = ap.parse_args(argv)
-    for ck in a.ckpt:
-        r = evaluate(a.exp, ck, a.limit, a.seed, a.device)
-        print(json.dumps({"checkpoint": ck, "loss_mel": r["loss_mel"], "loss_kl": r["loss_kl"],
-                          "scored": r["scored"], "skipped": r["skipped"]}), flush=True)
+    if a.d_ckpt is not None and len(a.d_ckpt) != len(a.ckpt):
+        ap.error(f"--d-ckpt was given {len(a.d_ckpt)} times, --ckpt {len(a.ckpt)}: one D per G, in order")
+    for n, ck in enumerate(a.ckpt):
+        dk = a.d_ckpt[n] if a.d_ckpt is not None else None
+        r = evaluate(a.exp, ck, a.limit, a.seed, a.device, d_checkpoint=dk)
+        line = {"checkpoint": ck, "loss_mel": r["loss_mel"], "loss_kl": r["loss_kl"],
+                "scored": r["scored"], "skipped": r["skipped"]}
+        if dk is not None:
+            line.update(d_checkpoint=dk, **{k: r[k] for k in D_LOSSES + ("loss_gen_all",)})
+        print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":

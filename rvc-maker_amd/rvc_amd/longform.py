@@ -25,6 +25,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from .pipeline import segment_plan
 from .shard import gather_waveforms, shard_utterances
 
 HALO = 1024  # frames each side; the U-Net's receptive-field radius is ~845 frames
@@ -102,10 +103,8 @@ def pipeline_sharded(vc, model, net_g, sid, audio, pitch, version, protect, dist
                      halo: int = HALO):
     """VC.pipeline_device of ONE utterance over all ranks of ``dist`` (see the module note).  ``audio``:
     the whole 16 kHz input on every rank (device f32 [N] or numpy)."""
-    import numpy as np
     rank, world = dist.get_rank(), dist.get_world_size()
-    if not torch.is_tensor(audio):
-        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(vc.device)
+    audio = vc._device_f32(audio)
     N = audio.numel()
     long_input = N + vc.window > vc.t_max
     xp, xp64 = vc.filt(audio.contiguous(), vc.t_pad, want_f64=long_input and rank == 0)
@@ -117,14 +116,8 @@ def pipeline_sharded(vc, model, net_g, sid, audio, pitch, version, protect, dist
     p_len = xp.numel() // vc.window
     coarse, pitchf = sharded_f0(vc, xp, pitch, dist, halo)
     coarse, pitchf = coarse[:p_len], pitchf[:p_len]
-    w, tp = vc.window, vc.t_pad_tgt
-    segs, s = [], 0  # convert.py:419-447, as VC._pipeline_on_device
-    for t in opt_ts:
-        t = t // w * w
-        segs.append((s, t + vc.t_pad2 + w, s // w, (t + vc.t_pad2) // w))
-        s = t
-    last = opt_ts[-1] // w * w if opt_ts else None
-    segs.append((last or 0, xp.numel(), (last or 0) // w, None))
+    tp = vc.t_pad_tgt
+    segs = segment_plan(opt_ts, xp.numel(), vc.window, vc.t_pad2)
     mine = shard_utterances([bb - aa for aa, bb, _, _ in segs], world)[rank]
     outs = []
     for si in mine:
@@ -142,7 +135,4 @@ def pipeline_sharded(vc, model, net_g, sid, audio, pitch, version, protect, dist
         for si, part in zip(owner[r], got[r]):
             pieces[si] = part.to(xp.device)
     out = torch.cat(pieces) if len(pieces) > 1 else pieces[0].contiguous()
-    if vc._ws is None:
-        vc._ws = torch.zeros(4, dtype=torch.int32, device=out.device)
-    ops.peak_normalize(out, vc._ws)
-    return out
+    return vc._peak_normalize(out)

@@ -46,6 +46,40 @@ from .f0 import RMVPE_LEGACY, F0Bank
 BH, AH = signal.butter(N=5, Wn=48, btype="high", fs=16000)  # convert.py:30
 
 
+def segment_plan(opt_ts, n, window, t_pad2):
+    """Segments of convert.py:419-447 over a padded signal of n samples: [s, t + t_pad2 + window) for each quiet
+    point t (rounded down to a frame), then [t, n).  -> [(a, b, fa, fb)]: samples [a, b) and f0 frames [fa, fb) per
+    segment, fb None for the last (the C++ host's vc_segments is the same plan)."""
+    segs, s = [], 0
+    for t in opt_ts:
+        t = t // window * window
+        segs.append((s, t + t_pad2 + window, s // window, (t + t_pad2) // window))
+        s = t
+    segs.append((s, n, s // window, None))
+    return segs
+
+
+def _phone_len(feats, p_len, n_pitch):
+    """T of the phone sequence for features [E][Tf] (convert.py:364-370), refusing what VC.pipeline never
+    produces."""
+    T = min(2 * feats.shape[1], p_len)
+    if 2 * feats.shape[1] > p_len:
+        raise NotImplementedError("phone longer than p_len (x_mask padding) never occurs in VC.pipeline")
+    if n_pitch < T:
+        raise ValueError("pitch shorter than the phone sequence")
+    return T
+
+
+def _phone_into(phone, feats, pitchf, protect, index, index_rate):
+    """Retrieval, then the phone upsample + protect blend (convert.py:347-378) of features [E][Tf] into the
+    view phone [E][T]."""
+    feats0 = feats  # convert.py:347: the protect blend uses the pre-retrieval features
+    if index is not None and index_rate != 0:
+        feats = index.retrieve_cf(feats, index_rate)
+    (E, Tf), T = feats.shape, phone.shape[1]
+    ops.phone_upsample(feats, feats0, pitchf[:T] if protect < 0.5 else None, phone, E, Tf, T, float(protect))
+
+
 class _CuMaskedStream:
     """One stream restricted to part of the chip (rvc_stream_create_cu_mask), owned by a VC: ``close`` waits for
     its work and destroys it (rvc_stream_destroy).  Left to process teardown, such a stream crashed rocprofv3's
@@ -190,11 +224,13 @@ class VC(F0Bank):
         return model.embed_cf(a0, version, self.embed_suffix)
 
     def voice_conversion_device(self, model, net_g, sid, a0, pitch, pitchf, version, protect, seg, feats=None,
-                                index=None, index_rate=0.0):
-        """VC.voice_conversion (convert.py:328-386) on a device segment a0 [N] -> waveform [T*upp]."""
+                                index=None, index_rate=0.0, seed=None):
+        """VC.voice_conversion (convert.py:328-386) on a device segment a0 [N] -> waveform [T*upp].  The noise is
+        drawn with ``seed`` (default ``self.seed + seg``)."""
+        seed = self.seed + seg if seed is None else seed
         prep = self.prior_device(model, net_g, sid, a0, pitch, pitchf, version, protect, seg, feats, index,
-                                 index_rate, self.seed + seg)
-        return self.generate_device(net_g, prep, seg, self.seed + seg)
+                                 index_rate, seed)
+        return self.generate_device(net_g, prep, seg, seed)
 
     def prior_device(self, model, net_g, sid, a0, pitch, pitchf, version, protect, seg, feats=None, index=None,
                      index_rate=0.0, seed=0):
@@ -204,20 +240,10 @@ class VC(F0Bank):
         N = a0.numel()
         if feats is None:
             feats = self.features_device(model, a0, version)
-        feats0 = feats  # convert.py:347: the protect blend uses the pre-retrieval features
-        if index is not None and index_rate != 0:
-            feats = index.retrieve_cf(feats, index_rate)
-        E, Tf = feats.shape
-        p_len = N // self.window
-        T = min(2 * Tf, p_len)  # convert.py:364-370
-        if 2 * Tf > p_len:
-            raise NotImplementedError("phone longer than p_len (x_mask padding) never occurs in VC.pipeline")
+        T = _phone_len(feats, N // self.window, pitch.numel())
+        phone = torch.empty(feats.shape[0], T, device=a0.device)
+        _phone_into(phone, feats, pitchf, protect, index, index_rate)
         pitch, pitchf = pitch[:T], pitchf[:T]
-        if pitch.numel() < T:
-            raise ValueError("pitch shorter than the phone sequence")
-        phone = torch.empty(E, T, device=a0.device)
-        blend = protect < 0.5
-        ops.phone_upsample(feats, feats0, pitchf if blend else None, phone, E, Tf, T, float(protect))
         zn = self.noise_fn(seg, "z", (1, net_g.inter, T)) if self.noise_fn else None
         z, _, _, gc = net_g.prior_cf(phone, pitch.contiguous(), sid, zn, seed)
         return {"z": z, "gc": gc, "pitchf": pitchf.contiguous(), "T": T}
@@ -251,27 +277,16 @@ class VC(F0Bank):
         B = len(items)
         phone = pitch = pf = None
         for b, (xp, coarse, pitchf, feats) in enumerate(items):
-            p_len = xp.numel() // self.window
-            feats0 = feats  # convert.py:347: the protect blend uses the pre-retrieval features
-            if index is not None and index_rate != 0:
-                feats = index.retrieve_cf(feats, index_rate)
-            E, Tf = feats.shape
-            T = min(2 * Tf, p_len)  # convert.py:364-370
-            if 2 * Tf > p_len:
-                raise NotImplementedError("phone longer than p_len (x_mask padding) never occurs in VC.pipeline")
+            T = _phone_len(feats, xp.numel() // self.window, coarse.numel())
             if phone is None:
-                phone = torch.empty(B, E, T, device=xp.device)
+                phone = torch.empty(B, feats.shape[0], T, device=xp.device)
                 pitch = torch.empty(B, T, dtype=coarse.dtype, device=xp.device)
                 pf = torch.empty(B, T, dtype=pitchf.dtype, device=xp.device)
             elif phone.shape[2] != T:
                 raise ValueError("voice_conversion_batch_device: clips of one length")
-            if coarse.numel() < T:
-                raise ValueError("pitch shorter than the phone sequence")
-            ops.phone_upsample(feats, feats0, pitchf[:T] if protect < 0.5 else None, phone[b], E, Tf, T,
-                               float(protect))
+            _phone_into(phone[b], feats, pitchf, protect, index, index_rate)
             pitch[b].copy_(coarse[:T])
             pf[b].copy_(pitchf[:T])
-        T = phone.shape[2]
         zn = None
         segs = noise_segs or [0] * B
         if self.noise_fn:
@@ -289,8 +304,7 @@ class VC(F0Bank):
                         volume_envelope=1.0, hop_length=64):
         """The hot path with inputs and output in HBM: audio device f32 [N] at 16 kHz (numpy accepted)
         -> device f32 waveform at tgt_sr.  filtfilt + reflect padding run on the device (f64)."""
-        if not torch.is_tensor(audio):
-            audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device)
+        audio = self._device_f32(audio)
         N = audio.numel()
         long_input = N + self.window > self.t_max  # convert.py:406 (audio padded by window/2 each side)
         xp, xp64 = self.filt(audio.contiguous(), self.t_pad,
@@ -299,12 +313,109 @@ class VC(F0Bank):
         if long_input:  # quiet-point search on the filtered f64 signal (device; the plan reads the points back)
             opt_ts = ops.quiet_points(xp64[self.t_pad: self.t_pad + N], self.window, self.t_center, self.t_query,
                                       self.t_max)
-        p_len = xp.numel() // self.window
+        segs = segment_plan(opt_ts, xp.numel(), self.window, self.t_pad2)
         f0_opts = dict(f0_autotune=f0_autotune, f0_autotune_strength=f0_autotune_strength, inp_f0=inp_f0,
                        hop_length=hop_length)
-        src64 = xp64[self.t_pad: self.t_pad + N] if volume_envelope != 1 else None
-        return self._pipeline_on_device(model, net_g, sid, xp, opt_ts, p_len, pitch, version, protect, index,
-                                        index_rate, f0_method, f0_opts, volume_envelope, src64, xp64)
+        # f0 over the whole padded signal, the features of every segment beside it
+        coarse, pitchf, feats = self._f0_features(
+            torch.cuda.current_stream(xp.device), self._side_stream(xp.device), model, version, xp, [xp64],
+            [xp[a:b] for a, b, _, _ in segs], pitch, f0_method, f0_opts)
+        p_len, tp = xp.numel() // self.window, self.t_pad_tgt
+        coarse, pitchf = coarse[:p_len], pitchf[:p_len]
+        outs = []
+        for seg, ((a, b, fa, fb), fe) in enumerate(zip(segs, feats)):
+            o = self.voice_conversion_device(model, net_g, sid, xp[a:b], coarse[fa:fb], pitchf[fa:fb], version,
+                                             protect, seg, feats=fe, index=index, index_rate=index_rate)
+            outs.append(o[tp: o.numel() - tp])
+        out = torch.cat(outs) if len(outs) > 1 else outs[0].contiguous()
+        if volume_envelope != 1:  # convert.py:449: both envelopes at the 16 kHz rate (reference quirk)
+            ops.change_rms(None, xp64[self.t_pad: self.t_pad + N], out, self.sample_rate // 2, volume_envelope)
+        self._peak_normalize(out)
+        if os.environ.get("RVC_AMD_CHECK"):  # debugging: synchronous check inside the device pass
+            self.check_errors()
+        return out
+
+    def _device_f32(self, audio):
+        """A clip as given (device tensor, or numpy / a sequence) -> device f32 tensor."""
+        if torch.is_tensor(audio):
+            return audio
+        return torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device)
+
+    def _peak_normalize(self, out):
+        """ops.peak_normalize in place, with this VC's 4-word workspace (allocated on first use) -> out."""
+        if self._ws is None:
+            self._ws = torch.zeros(4, dtype=torch.int32, device=out.device)
+        ops.peak_normalize(out, self._ws)
+        return out
+
+    def _f0_features(self, main, side, model, version, xp, x64s, feat_src, pitch, f0_method, f0_opts):
+        """The fork / join every pass runs, issued with ``main`` current: f0 of the filtered signal on ``side``,
+        the embedder features of ``feat_src`` (a tensor, or a list of segment slices -> a list) on ``main`` beside
+        it, joined by an event.  xp: one clip [Np] (never stacked: a stack is a copy launch) with x64s = [its f64
+        copy or None], or a stack [B][Np] with one entry of x64s per clip.  A stack goes through the batched RMVPE
+        (U-Net, W_ih, the B BiGRU recurrences side by side) for "rmvpe" / "rmvpe-legacy", else through ``f0_device``
+        clip by clip.  -> (coarse, pitchf, feats), safe to use on ``main``.
+
+        RMVPE / CREPE and ContentVec are independent until the synthesizer, and RMVPE's BiGRU recurrence occupies
+        only 32 CUs, so the two run concurrently."""
+        ready = torch.cuda.Event()
+        ready.record(main)
+        with torch.cuda.stream(side):
+            side.wait_event(ready)
+            if xp.dim() == 1:
+                coarse, pitchf = self.f0_device(xp, pitch, f0_method, xp64=x64s[0], **f0_opts)
+            elif f0_method in ("rmvpe", RMVPE_LEGACY):
+                coarse, pitchf = self._rmvpe().f0_device_batch(xp, 0.03, float(pitch),
+                                                               f0_range=self._rmvpe_range(f0_method))
+            else:
+                pairs = [self.f0_device(x, pitch, f0_method, xp64=x64, **f0_opts) for x, x64 in zip(xp, x64s)]
+                coarse, pitchf = torch.stack([c for c, _ in pairs]), torch.stack([f for _, f in pairs])
+            f0_done = torch.cuda.Event()
+            f0_done.record(side)
+        if isinstance(feat_src, list):
+            feats = [self.features_device(model, s, version) for s in feat_src]
+        else:
+            feats = self.features_device(model, feat_src, version)
+        main.wait_event(f0_done)
+        for t in (coarse, pitchf):
+            t.record_stream(main)
+        for t in (xp, *x64s):
+            if t is not None:
+                t.record_stream(side)
+        return coarse, pitchf, feats
+
+    def _group_front(self, main, side, model, version, group, pitch, f0_method, hop_length):
+        """The front end of a group of equal-length clips, issued with ``main`` current: filtfilt per clip (with
+        the f64 copy "pm" reads), then ``_f0_features`` over the stack of the group -- over the clip itself for a
+        group of one -> [(xp, coarse, pitchf, feats)] per clip."""
+        filtered = [self.filt(a.contiguous(), self.t_pad, want_f64=f0_method == "pm") for a in group]
+        xps, x64s = [f for f, _ in filtered], [f for _, f in filtered]
+        xp = torch.stack(xps) if len(group) > 1 else xps[0]
+        coarse, pitchf, feats = self._f0_features(main, side, model, version, xp, x64s, xp, pitch, f0_method,
+                                                  dict(hop_length=hop_length))
+        if xp.dim() == 1:
+            return [(xp, coarse, pitchf, feats)]
+        return [(xp[b], coarse[b], pitchf[b], feats[b]) for b in range(len(group))]
+
+    def _group_back(self, model, net_g, sid, items, version, protect, index, index_rate, seeds, noise_segs=None):
+        """The back end of a group, items as ``_group_front`` gives them: one B-clip synthesizer
+        (``voice_conversion_batch_device``; a group of one or RVC_AMD_SYNTH_BATCH=0: ``voice_conversion_device``
+        per clip), clip b drawing its noise with seeds[b] (parity mode: noise_fn of segment noise_segs[b], default
+        0).  A generator of the trimmed, peak-normalised waveforms in order: each is finished on the current
+        stream when it is yielded, so the caller's work on it is queued ahead of the next clip's.  The launches are
+        issued as the generator is consumed: consume it inside the stream context they belong to."""
+        tp = self.t_pad_tgt
+        if len(items) > 1 and self.SYNTH_BATCH:
+            ob = self.voice_conversion_batch_device(model, net_g, sid, items, version, protect, index, index_rate,
+                                                    seeds, noise_segs)
+            for b in range(len(items)):
+                yield self._peak_normalize(ob[b, tp: ob.shape[1] - tp])
+            return
+        for (xp, coarse, pitchf, feats), seed, seg in zip(items, seeds, noise_segs or [0] * len(items)):
+            p_len = xp.numel() // self.window
+            o = self.voice_conversion_device(model, net_g, sid, xp, coarse[:p_len], pitchf[:p_len], version, protect,
+                                             seg, feats=feats, index=index, index_rate=index_rate, seed=seed)
+            yield self._peak_normalize(o[tp: o.numel() - tp])
 
     def pipeline_device_batch(self, model, net_g, sid, audios, pitch, version, protect, index=None, index_rate=0.0,
                               f0_method="rmvpe", hop_length=64):
@@ -313,56 +424,20 @@ class VC(F0Bank):
         and ContentVec run as B-batched launches on their two streams, then the synthesizer as B-clip launches
         (``voice_conversion_batch_device``; RVC_AMD_SYNTH_BATCH=0: per clip).  Clip b draws its noise with seed
         ``self.seed + b``: it equals ``pipeline_device`` of that clip with ``seed = self.seed + b``, up to the
-        summation order of the batched launches (split-K / split-KV follow the batched grid).  Clips must fit one
+        summation order of the batched launches (split-K / split-KV follow the batched grid; a lone clip is not
+        stacked and runs its own launches, as in the clip stream).  Clips must fit one
         segment (N + window <= t_max, 41 s).  "rmvpe-legacy" batches as "rmvpe" does; ``hop_length`` goes to the f0
         methods that read it (``f0_device``)."""
         B = len(audios)
-        audios = [a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(
-            self.device) for a in audios]
+        audios = [self._device_f32(a) for a in audios]
         N = audios[0].numel()
         if any(a.numel() != N for a in audios) or N + self.window > self.t_max:
             raise ValueError("pipeline_device_batch: equal-length clips of at most t_max samples")
-        xpb = torch.stack([self.filt(a.contiguous(), self.t_pad)[0] for a in audios])  # [B][Np]
-        p_len = xpb.shape[1] // self.window
-        main = torch.cuda.current_stream(xpb.device)
-        side = self._side_stream(xpb.device)
-        ready = torch.cuda.Event()
-        ready.record(main)
-        with torch.cuda.stream(side):
-            side.wait_event(ready)
-            if f0_method in ("rmvpe", RMVPE_LEGACY):
-                coarse, pitchf = self._rmvpe().f0_device_batch(xpb, 0.03, float(pitch),
-                                                               f0_range=self._rmvpe_range(f0_method))
-            else:
-                pairs = [self.f0_device(xpb[b], pitch, f0_method, hop_length=hop_length) for b in range(B)]
-                coarse, pitchf = torch.stack([c for c, _ in pairs]), torch.stack([f for _, f in pairs])
-            f0_done = torch.cuda.Event()
-            f0_done.record(side)
-        feats = self.features_device(model, xpb, version)
-        main.wait_event(f0_done)
-        for t in (coarse, pitchf):
-            t.record_stream(main)
-        xpb.record_stream(side)
-        tp = self.t_pad_tgt
-        if self._ws is None:
-            self._ws = torch.zeros(4, dtype=torch.int32, device=xpb.device)
-        outs = []
-        if B > 1 and self.SYNTH_BATCH:
-            items = [(xpb[b], coarse[b], pitchf[b], feats[b]) for b in range(B)]
-            ob = self.voice_conversion_batch_device(model, net_g, sid, items, version, protect, index, index_rate,
-                                                    [self.seed + b for b in range(B)], list(range(B)))
-            for b in range(B):
-                out = ob[b, tp: ob.shape[1] - tp]
-                ops.peak_normalize(out, self._ws)
-                outs.append(out)
-            return outs
-        for b in range(B):
-            o = self.voice_conversion_device(model, net_g, sid, xpb[b], coarse[b, :p_len], pitchf[b, :p_len], version,
-                                             protect, b, feats=feats[b], index=index, index_rate=index_rate)
-            out = o[tp: o.numel() - tp]
-            ops.peak_normalize(out, self._ws)
-            outs.append(out)
-        return outs
+        dev = audios[0].device
+        items = self._group_front(torch.cuda.current_stream(dev), self._side_stream(dev), model, version, audios,
+                                  pitch, f0_method, hop_length)
+        return list(self._group_back(model, net_g, sid, items, version, protect, index, index_rate,
+                                     [self.seed + b for b in range(B)], list(range(B))))
 
     def pipeline_device_stream(self, model, net_g, sid, audios, pitch, version, protect, index=None, index_rate=0.0,
                                f0_method="rmvpe", batch=1, events=None, seeds=None, host_out=None, hop_length=64):
@@ -395,8 +470,11 @@ class VC(F0Bank):
                 ev.record(stream)
                 events.append((role, g, ev))
 
-        audios = [a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(
-            self.device) for a in audios]
+        if seeds is not None and len(seeds) != len(audios):
+            raise ValueError("pipeline_device_stream: one seed per clip")
+        if host_out is not None and len(host_out) != len(audios):
+            raise ValueError("pipeline_device_stream: one host buffer per clip")
+        audios = [self._device_f32(a) for a in audios]
         if any(a.numel() + self.window > self.t_max for a in audios):
             raise ValueError("pipeline_device_stream: clips of at most t_max samples (one segment each)")
         if not audios:
@@ -410,22 +488,7 @@ class VC(F0Bank):
         # front pipelines (front + fside stream pairs) taken in turn by consecutive groups, so that one
         # group's latency-bound front end (U-Net launches, the BiGRU recurrence) overlaps the next one's
         fronts = [(self._aux_stream(dev, "front", i), self._aux_stream(dev, "fside", i)) for i in range(self.FRONTS)]
-        if self._ws is None:
-            self._ws = torch.zeros(4, dtype=torch.int32, device=dev)
-        seed0, tp = self.seed, self.t_pad_tgt
-        if seeds is not None and len(seeds) != len(audios):
-            raise ValueError("pipeline_device_stream: one seed per clip")
-        if host_out is not None and len(host_out) != len(audios):
-            raise ValueError("pipeline_device_stream: one host buffer per clip")
-        seed_of = (lambda k: int(seeds[k])) if seeds is not None else (lambda k: seed0 + k)
-
-        def emit(out):
-            outs.append(out)
-            if host_out is not None:
-                # D2H of this clip on the back stream, right behind its synthesizer.  (On the caller's stream it made
-                # the caller wait for each clip, and the front streams wait for the caller before every group: the
-                # front end then never ran more than one clip ahead -- round 5 timeline, the back stream idle 35 %.)
-                host_out[len(outs) - 1][: out.numel()].copy_(out, non_blocking=True)
+        seed_of = (lambda k: int(seeds[k])) if seeds is not None else (lambda k: self.seed + k)
 
         def issue_front(group, g):
             """front end of one group on the front / fside streams -> ([(xp, coarse, pitchf, feats)], event).
@@ -437,37 +500,7 @@ class VC(F0Bank):
                 mark("front_start", g, front)
                 for a in group:
                     a.record_stream(front)
-                pm = f0_method == "pm"  # pm reads the f64 filtered signal
-                filtered = [self.filt(a.contiguous(), self.t_pad, want_f64=pm) for a in group]
-                xps, x64s = [f for f, _ in filtered], [f for _, f in filtered]
-                xp = xps[0] if len(group) == 1 else torch.stack(xps)
-                ready = torch.cuda.Event()
-                ready.record(front)
-                with torch.cuda.stream(side):
-                    side.wait_event(ready)
-                    if len(group) == 1:
-                        coarse, pitchf = self.f0_device(xp, pitch, f0_method, xp64=x64s[0], hop_length=hop_length)
-                    elif f0_method in ("rmvpe", RMVPE_LEGACY):
-                        coarse, pitchf = self._rmvpe().f0_device_batch(xp, 0.03, float(pitch),
-                                                                       f0_range=self._rmvpe_range(f0_method))
-                    else:
-                        pairs = [self.f0_device(xp[b], pitch, f0_method, xp64=x64s[b], hop_length=hop_length)
-                                 for b in range(len(group))]
-                        coarse, pitchf = torch.stack([c for c, _ in pairs]), torch.stack([f for _, f in pairs])
-                    f0_done = torch.cuda.Event()
-                    f0_done.record(side)
-                feats = self.features_device(model, xp, version)
-                front.wait_event(f0_done)
-                for t in (coarse, pitchf):
-                    t.record_stream(front)
-                xp.record_stream(side)
-                for t in x64s:
-                    if t is not None:
-                        t.record_stream(side)
-                if len(group) == 1:
-                    items = [(xp, coarse, pitchf, feats)]
-                else:
-                    items = [(xp[b], coarse[b], pitchf[b], feats[b]) for b in range(len(group))]
+                items = self._group_front(front, side, model, version, group, pitch, f0_method, hop_length)
                 done = torch.cuda.Event()
                 done.record(front)
                 mark("front_end", g, front)
@@ -475,38 +508,26 @@ class VC(F0Bank):
 
         outs = []
         nxt = issue_front(groups[0], 0)
-        try:
-            for g in range(len(groups)):
-                items, done = nxt
-                if g + 1 < len(groups):
-                    nxt = issue_front(groups[g + 1], g + 1)  # queued ahead of group g's synthesizers
-                with torch.cuda.stream(back):
-                    back.wait_event(done)
-                    mark("back_start", g, back)
-                    for it in items:
-                        for t in it:
-                            t.record_stream(back)
-                    if len(items) > 1 and self.SYNTH_BATCH:
-                        gseeds = [seed_of(len(outs) + b) for b in range(len(items))]
-                        ob = self.voice_conversion_batch_device(model, net_g, sid, items, version, protect, index,
-                                                                index_rate, gseeds)
-                        for b in range(len(items)):
-                            out = ob[b, tp: ob.shape[1] - tp]
-                            ops.peak_normalize(out, self._ws)
-                            emit(out)
-                        items = []
-                    for xp, coarse, pitchf, feats in items:
-                        p_len = xp.numel() // self.window
-                        self.seed = seed_of(len(outs))
-                        o = self.voice_conversion_device(model, net_g, sid, xp, coarse[:p_len], pitchf[:p_len],
-                                                         version, protect, 0, feats=feats, index=index,
-                                                         index_rate=index_rate)
-                        out = o[tp: o.numel() - tp]
-                        ops.peak_normalize(out, self._ws)
-                        emit(out)
-                    mark("back_end", g, back)
-        finally:
-            self.seed = seed0
+        for g in range(len(groups)):
+            items, done = nxt
+            if g + 1 < len(groups):
+                nxt = issue_front(groups[g + 1], g + 1)  # queued ahead of group g's synthesizers
+            with torch.cuda.stream(back):
+                back.wait_event(done)
+                mark("back_start", g, back)
+                for it in items:
+                    for t in it:
+                        t.record_stream(back)
+                gseeds = [seed_of(len(outs) + b) for b in range(len(items))]
+                for out in self._group_back(model, net_g, sid, items, version, protect, index, index_rate, gseeds):
+                    outs.append(out)
+                    if host_out is not None:
+                        # D2H of this clip on the back stream, right behind its synthesizer.  (On the caller's stream
+                        # it made the caller wait for each clip, and the front streams wait for the caller before
+                        # every group: the front end then never ran more than one clip ahead -- round 5 timeline,
+                        # the back stream idle 35 %.)
+                        host_out[len(outs) - 1][: out.numel()].copy_(out, non_blocking=True)
+                mark("back_end", g, back)
         caller.wait_stream(back)
         for o in outs:
             o.record_stream(caller)
@@ -612,52 +633,6 @@ class VC(F0Bank):
         prio = self.side_priority if getattr(self, "side_priority", None) is not None \
             else int(os.environ.get("RVC_AMD_SIDE_PRIORITY", dflt))
         return self._pooled_stream(device, prio, self.STREAM_SLOT["side"])
-
-    def _pipeline_on_device(self, model, net_g, sid, xp, opt_ts, p_len, pitch, version, protect, index=None,
-                            index_rate=0.0, f0_method="rmvpe", f0_opts=None, volume_envelope=1.0, src64=None, xp64=None):
-        # Segments of convert.py:419-440: [s, t + t_pad2 + w) for each quiet point t, then [t, end).
-        w, tp = self.window, self.t_pad_tgt
-        segs, s = [], 0
-        for t in opt_ts:
-            t = t // w * w
-            segs.append((s, t + self.t_pad2 + w, s // w, (t + self.t_pad2) // w))
-            s = t
-        last = opt_ts[-1] // w * w if opt_ts else None
-        segs.append((last or 0, xp.numel(), (last or 0) // w, None))
-        # RMVPE (f0 over the whole padded signal) runs on a side stream, concurrently with the
-        # ContentVec features of every segment on the main stream: the two networks are independent
-        # until the synthesizer, and RMVPE's BiGRU recurrence occupies only 32 CUs.
-        main = torch.cuda.current_stream(xp.device)
-        side = self._side_stream(xp.device)
-        ready = torch.cuda.Event()
-        ready.record(main)
-        with torch.cuda.stream(side):
-            side.wait_event(ready)
-            coarse, pitchf = self.f0_device(xp, pitch, f0_method, xp64=xp64, **(f0_opts or {}))
-            f0_done = torch.cuda.Event()
-            f0_done.record(side)
-        feats = [self.features_device(model, xp[a:b], version) for a, b, _, _ in segs]
-        main.wait_event(f0_done)
-        coarse.record_stream(main)
-        pitchf.record_stream(main)
-        xp.record_stream(side)
-        if xp64 is not None:
-            xp64.record_stream(side)
-        coarse, pitchf = coarse[:p_len], pitchf[:p_len]
-        outs = []
-        for seg, ((a, b, fa, fb), fe) in enumerate(zip(segs, feats)):
-            o = self.voice_conversion_device(model, net_g, sid, xp[a:b], coarse[fa:fb], pitchf[fa:fb], version,
-                                             protect, seg, feats=fe, index=index, index_rate=index_rate)
-            outs.append(o[tp: o.numel() - tp])
-        out = torch.cat(outs) if len(outs) > 1 else outs[0].contiguous()
-        if volume_envelope != 1:  # convert.py:449: both envelopes at the 16 kHz rate (reference quirk)
-            ops.change_rms(None, src64, out, self.sample_rate // 2, volume_envelope)
-        if self._ws is None:
-            self._ws = torch.zeros(4, dtype=torch.int32, device=xp.device)
-        ops.peak_normalize(out, self._ws)
-        if os.environ.get("RVC_AMD_CHECK"):  # debugging: synchronous check inside the device pass
-            self.check_errors()
-        return out
 
     def check_errors(self):
         """Raise if a device-side failure was flagged since the last check: the RMVPE BiGRU's hand-off

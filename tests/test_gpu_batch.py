@@ -194,6 +194,30 @@ def test_batched_stream_bit_identical_to_batch(models):
     vc.check_errors()
 
 
+def test_pm_batch_matches_per_clip_and_stream(models):
+    """f0_method "pm" (which reads the f64 filtered signal) through the batched pass: pipeline_device_batch gives each
+    clip the waveform of pipeline_device at seed + b (f0 is per clip on both sides, only ContentVec and the
+    synthesizer are batched: the bar of test_pipeline_batch_matches_per_clip), and pipeline_device_stream(batch=2)
+    equals that batch bit for bit."""
+    hub, _, net_g, vc = models
+    xs = clips(2, 2.0, 600)
+    vc.seed = 30
+    outs = vc.pipeline_device_batch(hub, net_g, 0, xs, 0, "v2", 0.33, f0_method="pm")
+    got = vc.pipeline_device_stream(hub, net_g, 0, xs, 0, "v2", 0.33, f0_method="pm", batch=2)
+    torch.cuda.synchronize()
+    assert len(outs) == len(got) == 2
+    for b, x in enumerate(xs):
+        vc.seed = 30 + b
+        ref = vc.pipeline_device(hub, net_g, 0, x, 0, "v2", 0.33, f0_method="pm")
+        assert outs[b].shape == ref.shape
+        rel = ((outs[b] - ref).double().pow(2).mean().sqrt() / ref.double().pow(2).mean().sqrt()).item()
+        print(f"pm clip {b}: batch vs per-clip relative rms {rel:.3e}")
+        assert rel <= 1e-4, (b, rel)
+        assert torch.equal(got[b], outs[b]), (b, (got[b] - outs[b]).abs().max().item())
+    vc.seed = 0
+    vc.check_errors()
+
+
 @pytest.mark.parametrize("C,K,dil", [(32, 3, 5), (64, 7, 3), (64, 11, 1)])
 def test_resblock_pair_batched_bit_identical(models, C, K, dil):
     """The fused ResBlock pair over [B][C][L]: each clip bit-identical to its own launch (per-tile scales and

@@ -1143,6 +1143,40 @@ int rvc_lsgan_terms(const float* d_r, const float* d_g, int64_t n, double* table
 int rvc_disc_finish(const double* table, int n_fm, int n_disc, const float* l1, float c_mel, const float* kl, float c_kl,
                     float* out, rvc_stream_t stream);
 
+/* The discriminator's training step (train.py:851-860) behind that forward (csrc/disc_backward.hip).  Convolutions are
+ * exact f32 FMA / MFMA chains in a fixed order, every reduction is fixed-order: two runs give the same bits.
+ * lsgan_grad: d [2 n], a discriminator's conv_post map, real half first -> dy [2 n], the gradient of
+ *   discriminator_loss times scale: -2 (1 - d_r) / n and 2 d_g / n.
+ * dyp below is dy * (y > 0 ? 1 : slope) with y the stored forward output of the layer that produced dy (a LeakyReLU
+ *   output has its input's sign; 0 takes the slope); y = NULL: no activation (conv_post).
+ * conv_bwd_data: dx[b][ci][i] = sum_co sum_k w[co][ci][k] dyp[b][co][j], i = j stride + k - pad, for Conv1d weights
+ *   w [Co][Ci / groups][K]; every row i < Lin is written.  groups = 1 with Ci >= 16 runs on v_mfma_f32_16x16x4_f32
+ *   per stride phase, anything else directly.
+ * conv_bwd_weight: dW[co][ci][k] (+)= scale sum_b sum_j dyp[b][co][j] x[b][ci][j stride + k - pad] and
+ *   db[co] (+)= scale sum_b sum_j dyp[b][co][j]; accumulate != 0 adds to what dW and db hold.  The sum over (b, j) is
+ *   split into chunks whose partials go to work (rvc_conv_bwd_weight_work_bytes asks for what it would like; any
+ *   buffer that holds dW once is enough) and are added in order.  period > 0: x is the signals [B / period][t] read as
+ *   DiscriminatorP's first conv reads them (rvc_period_front's reflected index and [Lin][period] view; Ci = 1).
+ * wn_adamw: one conv's rows.  From dW [Co][n], v [Co][n], g [Co]: dg = <dW, v> / |v|, dv = g / |v| (dW - v dg / |v|)
+ *   (the backward of torch._weight_norm(v, g, 0)); table[3 row + 0..2] = |dg|^2, |dv|^2, |db|^2 of the row; then
+ *   torch.optim.AdamW's update (amsgrad off) of g, v and bias with their exp_avg (m_*) and exp_avg_sq (s_*) in place,
+ *   step counting from 1.  f64 arithmetic on the f32 values, every stored value rounded once.
+ * grad_norm: out[0] = sqrt(sum of table[0 .. n)), clip_grad_value(parameters, None)'s return; work: RED_BLOCKS doubles
+ *   (rvc_disc_work_bytes() is enough). */
+int rvc_lsgan_grad(const float* d, float* dy, int64_t n, float scale, rvc_stream_t stream);
+int rvc_conv_bwd_data(const float* dy, const float* y, const float* w, float* dx, int64_t B, int64_t Ci, int64_t Co,
+                      int64_t Lin, int64_t Lout, int K, int stride, int pad, int groups, float slope,
+                      rvc_stream_t stream);
+int64_t rvc_conv_bwd_weight_work_bytes(int64_t B, int64_t Ci, int64_t Co, int64_t Lout, int K, int groups);
+int rvc_conv_bwd_weight(const float* dy, const float* y, const float* x, float* dW, float* db, int64_t B, int64_t Ci,
+                        int64_t Co, int64_t Lin, int64_t Lout, int K, int stride, int pad, int groups, float slope,
+                        float scale, int accumulate, int period, int64_t t, void* work, int64_t work_bytes,
+                        rvc_stream_t stream);
+int rvc_wn_adamw(const float* dW, const float* db, float* v, float* g, float* bias, float* m_v, float* s_v, float* m_g,
+                 float* s_g, float* m_b, float* s_b, int64_t Co, int64_t n, double lr, double beta1, double beta2,
+                 double eps, double weight_decay, int64_t step, double* table, rvc_stream_t stream);
+int rvc_grad_norm(const double* table, int64_t n, double* out, void* work, int64_t work_bytes, rvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -361,6 +361,16 @@ SIGNATURES = {
     "rvc_pair_l1": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p],
     "rvc_lsgan_terms": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p],
     "rvc_disc_finish": [c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p],
+    "rvc_lsgan_grad": [c_void_p, c_void_p, c_int64, c_float, c_void_p],
+    "rvc_conv_bwd_data": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int,
+                          c_int, c_int, c_int, c_float, c_void_p],
+    "rvc_conv_bwd_weight_work_bytes": [c_int64, c_int64, c_int64, c_int64, c_int, c_int],
+    "rvc_conv_bwd_weight": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                            c_int64, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int64, c_void_p,
+                            c_int64, c_void_p],
+    "rvc_wn_adamw": [c_void_p] * 11 + [c_int64, c_int64, c_double, c_double, c_double, c_double, c_double, c_int64,
+                                       c_void_p, c_void_p],
+    "rvc_grad_norm": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p],
 }
 _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_int64, "rvc_conv1d_x6_bytes": c_int64,
              "rvc_conv64_workspace_bytes": c_int64, "rvc_wino64_workspace_bytes": c_int64,
@@ -382,6 +392,7 @@ _RESTYPES = {"rvc_last_error": ctypes.c_char_p, "rvc_conv1d_workspace_bytes": c_
              "rvc_performer_work_bytes": c_int64,
              "rvc_spectrogram_frames": c_int64, "rvc_trainfwd_work_bytes": c_int64,
              "rvc_period_front_rows": c_int64, "rvc_disc_work_bytes": c_int64, "rvc_disc_table_slots": c_int64,
+             "rvc_conv_bwd_weight_work_bytes": c_int64,
              "rvc_lfilter64_warmup": c_int64, "rvc_lfilter64_work_bytes": c_int64, "rvc_frame_rms64_len": c_int64}
 
 _lib = None

@@ -100,6 +100,11 @@ class DiscriminatorAMD:
         model = ckpt["model"]
         check_supported(model, version)
         self.version, self.periods, self.device = version, PERIODS[version], device
+        self._build(model)
+
+    def _build(self, model: dict) -> dict:
+        """Fold the weight norm of a state dict on the host and put every conv on the device; returns the folded dict."""
+        version, device = self.version, self.device
         W = fold_weight_norm({k: model[k] for k in discriminator_keys(version)})
         w = lambda name: W[name + ".weight"]  # noqa: E731
         b = lambda name: W[name + ".bias"]  # noqa: E731
@@ -118,6 +123,7 @@ class DiscriminatorAMD:
             self.p_post.append(ops.Conv(w(pi + "conv_post").squeeze(-1), b(pi + "conv_post"), device=device))
         self.n_disc = 1 + len(self.periods)
         self.n_fm = len(S_CONVS) + 1 + len(self.periods) * (len(P_CHANNELS) + 1)
+        return W
 
     # ------------------------------------------------------------------ forward
     @staticmethod
@@ -178,6 +184,10 @@ class DiscriminatorAMD:
         if wave_slice.numel() != y_hat.numel():
             raise ValueError(f"losses: the wave slice has {wave_slice.numel()} samples, y_hat {y_hat.numel()}")
         fmaps = self._run(torch.stack([wave_slice.reshape(-1).float(), y_hat.reshape(-1).float()]))
+        return self._loss_vector_of(fmaps, l1, c_mel, kl, c_kl)
+
+    def _loss_vector_of(self, fmaps, l1=None, c_mel=1.0, kl=None, c_kl=1.0):
+        y_hat = fmaps[0][0]
         table = ops.disc_table(self.n_fm, self.n_disc, y_hat.device)
         work, _ = ops.disc_work(y_hat.device)
         slot = 0
@@ -215,3 +225,224 @@ class DiscriminatorAMD:
         if (loss_mel is None) != (loss_kl is None):
             raise ValueError("losses: loss_mel and loss_kl go together")
         return self.unpack(self.loss_vector(wave_slice, y_hat, loss_mel, c_mel, loss_kl, c_kl).cpu().numpy())
+
+
+# ---------------------------------------------------------------------------------------------- the training step
+WEIGHT_DECAY = 0.01  # torch.optim.AdamW's default: train.py:766 passes lr, betas and eps only
+
+
+def discriminator_convs(version: str) -> list:
+    """Per discriminator its convs in forward order as ``(name, stride, pad, groups, activation)``."""
+    out = [[(f"discriminators.0.convs.{j}", s, pad, g, True) for j, (_, _, _, s, g, pad) in enumerate(S_CONVS)] +
+           [("discriminators.0.conv_post", 1, 1, 1, False)]]
+    for i in range(1, len(PERIODS[version]) + 1):
+        out.append([(f"discriminators.{i}.convs.{j}", P_STRIDE, P_PAD, 1, True) for j in range(len(P_CHANNELS))] +
+                   [(f"discriminators.{i}.conv_post", 1, 1, 1, False)])
+    return out
+
+
+def check_trainable(ckpt: dict, version: str, hps_train: dict) -> None:
+    """What the discriminator's step refuses, by name, before anything is uploaded."""
+    check_supported(ckpt["model"], version)
+    if hps_train.get("fp16_run"):
+        raise NotImplementedError("rvc_amd: fp16_run / AMP training: the discriminator's step on the device is f32 "
+                                  "(no autocast, no GradScaler)")
+    for k in ("learning_rate", "betas", "eps"):
+        if k not in hps_train:
+            raise KeyError(f"rvc_amd: the experiment's config.json has no train.{k}")
+
+
+def check_pairs(pairs) -> int:
+    """The common length of the (wave slice, y_hat) pairs of one step."""
+    if not pairs:
+        raise ValueError("rvc_amd: a discriminator step needs at least one (wave slice, y_hat) pair")
+    sizes = {int(t.numel()) for pair in pairs for t in pair}
+    if len(sizes) != 1:
+        raise ValueError(f"rvc_amd: pairs of unequal length ({sorted(sizes)}): a step takes slices of one segment_size, as "
+                         "the reference's batch does")
+    return sizes.pop()
+
+
+def checkpoint_dict(version: str, model: dict, moments: dict, step: int, lr: float, betas, eps: float,
+                    iteration: int) -> dict:
+    """The dict ``save_checkpoint`` writes for ``net_d`` (train.py:269-271): ``model`` with ``.weight_g`` / ``.weight_v``
+    keys in the module's order, ``optimizer`` as ``torch.optim.AdamW.state_dict()`` lays it out -- parameter i is the
+    i-th key, ``net_d.parameters()``' order; ``moments`` = {key: (exp_avg, exp_avg_sq)}, empty before the first step
+    -- ``iteration`` and ``learning_rate``.  The reference's ``load_checkpoint`` and ``DiscriminatorAMD`` read it."""
+    from collections import OrderedDict
+    keys = discriminator_keys(version)
+    probe = torch.optim.AdamW([torch.zeros(1)], lr, betas=tuple(betas), eps=eps, weight_decay=WEIGHT_DECAY).state_dict()
+    group = dict(probe["param_groups"][0], params=list(range(len(keys))))
+    state = {}
+    if moments:
+        for i, (k, shape) in enumerate(keys.items()):
+            m, s = moments[k]
+            state[i] = {"step": torch.tensor(float(step)), "exp_avg": m.float().reshape(shape),
+                        "exp_avg_sq": s.float().reshape(shape)}
+    return {"model": OrderedDict((k, model[k].float().reshape(shape)) for k, shape in keys.items()),
+            "iteration": int(iteration), "optimizer": {"state": state, "param_groups": [group]}, "learning_rate": lr}
+
+
+class DiscriminatorTrainerAMD(DiscriminatorAMD):
+    """``net_d`` with its ``torch.optim.AdamW`` on the device: ``step`` is train.py:851-860 -- the forward on
+    ``(wave, y_hat.detach())``, ``discriminator_loss``, its backward, ``grad_norm_d`` and the optimizer step -- after which
+    ``forward`` and ``losses`` see the stepped weights, as the loop's second pass does (train.py:863-869).  No gradient
+    reaches ``y_hat``; the generator's step is not here.  ``hps_train`` is the ``train`` section of the experiment's
+    ``config.json``.  csrc/disc_backward.hip; DESIGN.md §20."""
+
+    def __init__(self, ckpt: dict, version: str = "v2", hps_train: dict = None, device: str = "cuda"):
+        if version not in PERIODS:
+            raise ValueError(f"rvc_amd: version {version!r}: the discriminator's periods are set for 'v1' and 'v2'")
+        hps_train = dict(hps_train or {})
+        check_trainable(ckpt, version, hps_train)
+        self.version, self.periods, self.device = version, PERIODS[version], device
+        self.keys = discriminator_keys(version)
+        self.convs = discriminator_convs(version)
+        self.names = [c[0] for convs in self.convs for c in convs]
+        opt = ckpt.get("optimizer") or {}
+        groups = opt.get("param_groups") or [{}]
+        self.lr = float(groups[0].get("lr", hps_train["learning_rate"]))
+        self.betas = tuple(float(b) for b in hps_train["betas"])
+        self.eps = float(hps_train["eps"])
+        self.iteration = int(ckpt.get("iteration", 0))
+        model, state = ckpt["model"], opt.get("state") or {}
+        index = {k: i for i, k in enumerate(self.keys)}
+        if state and len(state) != len(self.keys):
+            raise ValueError(f"rvc_amd: the optimizer state holds {len(state)} parameters, net_d has {len(self.keys)}")
+        self.step_count = int(float(state[0]["step"])) if state else 0
+        dev = lambda t: t.detach().float().reshape(-1).contiguous().to(device)  # noqa: E731
+        self.P, self.M, self.dW, self.db, self.rows = {}, {}, {}, {}, {}
+        row = 0
+        for name in self.names:
+            self.P[name] = tuple(dev(model[name + s]) for s in (".weight_g", ".weight_v", ".bias"))
+            moments = []
+            for s in (".weight_v", ".weight_g", ".bias"):  # rvc_wn_adamw's order: m_v, s_v, m_g, s_g, m_b, s_b
+                st = state.get(index[name + s]) if state else None
+                for m in ("exp_avg", "exp_avg_sq"):
+                    moments.append(dev(st[m]) if st else torch.zeros(model[name + s].numel(), device=device))
+            self.M[name] = tuple(moments)
+            self.dW[name] = torch.empty(self.keys[name + ".weight_v"][:3], device=device, dtype=torch.float32)
+            self.db[name] = torch.empty(self.keys[name + ".bias"], device=device, dtype=torch.float32)
+            self.rows[name] = row
+            row += self.keys[name + ".bias"][0]
+        self.table = torch.zeros(3 * row, device=device, dtype=torch.float64)
+        self.work = None
+        self._refold(model)
+
+    # ------------------------------------------------------------------ weights
+    def _model(self) -> dict:
+        """The parameters as a host state dict in the checkpoint's keys and shapes."""
+        out = {}
+        for name in self.names:
+            g, v, b = self.P[name]
+            out[name + ".bias"] = b.cpu()
+            out[name + ".weight_g"] = g.cpu().reshape(self.keys[name + ".weight_g"])
+            out[name + ".weight_v"] = v.cpu().reshape(self.keys[name + ".weight_v"])
+        return out
+
+    def _refold(self, model: dict = None):
+        """w = g v / |v| and the conv engine's packed images from the current parameters.  The fold runs where
+        ``DiscriminatorAMD`` runs it for a checkpoint -- ``torch._weight_norm`` on the host -- so that a saved step reloads to
+        the same bits; the parameters cross the host once per step (DESIGN.md §20 has the cost)."""
+        W = self._build(self._model() if model is None else model)
+        self.w = {name: W[name + ".weight"].reshape(self.keys[name + ".weight_v"][:3]).contiguous().to(self.device)
+                  for name in self.names}
+        self._dirty = False
+
+    def _run(self, y):
+        if self._dirty:
+            self._refold()
+        return super()._run(y)
+
+    # ------------------------------------------------------------------ the step
+    def _work(self, sig):
+        if self.work is None:
+            self.work = torch.empty(64 << 20, device=self.device, dtype=torch.uint8)
+        return self.work
+
+    def _backward(self, sig, fmaps, scale, accumulate):
+        """Gradients of ``scale * discriminator_loss`` of one pair (sig [2][t], its feature maps) into dW / db."""
+        work = self._work(sig)
+        for d, convs in enumerate(self.convs):
+            maps = fmaps[d]
+            dy = ops.lsgan_grad(maps[-1], scale)
+            for l in range(len(convs) - 1, -1, -1):
+                name, stride, pad, groups, act = convs[l]
+                y = maps[l] if act else None
+                first = l == 0
+                x = sig if first and d else sig.view(2, 1, -1) if first else maps[l - 1]
+                ops.conv_bwd_weight(dy, y, x, self.dW[name], self.db[name], stride, pad, groups, LRELU_SLOPE, 1.0,
+                                    accumulate, self.periods[d - 1] if first and d else 0, work)
+                if not first:  # a first conv's input is the signal: no gradient in this step
+                    dy = ops.conv_bwd_data(dy, y, self.w[name], x.shape[2], stride, pad, groups, LRELU_SLOPE)
+
+    def step(self, pairs) -> dict:
+        """One optimizer step of D on ``pairs`` = [(wave_slice, y_hat), ...] (f32 [segment_size] each, on the device):
+        the gradient of the reference's batch of those pairs (each pair's gradient at scale 1 / len(pairs), summed),
+        ``grad_norm_d`` as ``clip_grad_value(net_d.parameters(), None)`` returns it, one AdamW update.  Returns
+        ``loss_disc``, ``losses_disc_r``, ``losses_disc_g`` (the batch's means) and ``grad_norm_d``."""
+        check_pairs(pairs)
+        n = len(pairs)
+        vecs = []
+        for i, (wave, y_hat) in enumerate(pairs):
+            sig = torch.stack([wave.reshape(-1).float(), y_hat.detach().reshape(-1).float()]).contiguous()
+            fmaps = self._run(sig)
+            vecs.append(self._loss_vector_of(fmaps))
+            self._backward(sig, fmaps, 1.0 / n, i > 0)
+        self.step_count += 1
+        for name in self.names:
+            g, v, b = self.P[name]
+            r = self.rows[name]
+            ops.wn_adamw(self.dW[name], self.db[name], v, g, b, self.M[name], self.table[3 * r:3 * (r + g.numel())],
+                         self.lr, self.betas, self.eps, WEIGHT_DECAY, self.step_count)
+        norm = ops.grad_norm(self.table)
+        self._dirty = True
+        per = [self.unpack(v.cpu().numpy()) for v in vecs]
+        out = {"loss_disc": sum(p["loss_disc"] for p in per) / n,
+               "losses_disc_r": [sum(p["losses_disc_r"][i] for p in per) / n for i in range(self.n_disc)],
+               "losses_disc_g": [sum(p["losses_disc_g"][i] for p in per) / n for i in range(self.n_disc)],
+               "grad_norm_d": float(norm.item())}
+        return out
+
+    def gradients(self) -> dict:
+        """The last step's gradients of the folded weights and biases, ``{name: (dW [Co][Ci / groups][K], db [Co])}``."""
+        return {name: (self.dW[name], self.db[name]) for name in self.names}
+
+    # ------------------------------------------------------------------ state
+    def snapshot(self) -> dict:
+        """D and its optimizer state, to ``restore`` later: device copies of the parameters and moments, and the folded
+        weights as they are (a step replaces them, it does not write into them)."""
+        if self._dirty:
+            self._refold()
+        fwd = {k: getattr(self, k) for k in ("s_first", "s_grouped", "s_last", "s_post", "p_front", "p_convs", "p_post",
+                                             "w")}
+        return {"P": {k: tuple(t.clone() for t in v) for k, v in self.P.items()},
+                "M": {k: tuple(t.clone() for t in v) for k, v in self.M.items()},
+                "step": self.step_count, "lr": self.lr, "iteration": self.iteration, "fwd": fwd}
+
+    def restore(self, snap: dict) -> None:
+        for k, v in snap["P"].items():
+            for dst, src in zip(self.P[k], v):
+                dst.copy_(src)
+        for k, v in snap["M"].items():
+            for dst, src in zip(self.M[k], v):
+                dst.copy_(src)
+        self.step_count, self.lr, self.iteration = snap["step"], snap["lr"], snap["iteration"]
+        for k, v in snap["fwd"].items():
+            setattr(self, k, v)
+        self._dirty = False
+
+    def state_dict(self, iteration: int = None) -> dict:
+        """The dict ``save_checkpoint`` writes for ``net_d`` (``checkpoint_dict``)."""
+        slot = {"weight_v": 0, "weight_g": 2, "bias": 4}
+        moments = {}
+        if self.step_count:
+            for k in self.keys:
+                name, suffix = k.rsplit(".", 1)
+                m, j = self.M[name], slot[suffix]
+                moments[k] = (m[j].cpu(), m[j + 1].cpu())
+        return checkpoint_dict(self.version, self._model(), moments, self.step_count, self.lr, self.betas, self.eps,
+                               self.iteration if iteration is None else iteration)
+
+    def save(self, path: str, iteration: int = None) -> None:
+        torch.save(self.state_dict(iteration), path)

@@ -1469,4 +1469,109 @@ def disc_finish(table, n_fm, n_disc, l1=None, c_mel=1.0, kl=None, c_kl=1.0):
     return out
 
 
+# ------------------------------------------------------------------ the discriminator's step (disc_backward.hip)
+def lsgan_grad(d, scale=1.0, out=None):
+    """The gradient of discriminator_loss on one discriminator's conv_post map d (real half first, 2 n values) times
+    ``scale``: -2 (1 - d_r) / n and 2 d_g / n, in d's shape (rvc_lsgan_grad)."""
+    if d.numel() == 0 or d.numel() % 2 or not d.is_contiguous():
+        raise ValueError(f"lsgan_grad: a contiguous map of two halves, not {tuple(d.shape)}")
+    if out is None:
+        out = torch.empty_like(d)
+    check(_lib.load().rvc_lsgan_grad(_p(d), _p(out), d.numel() // 2, scale, _stream()), "lsgan_grad")
+    return out
+
+
+def _bwd_shapes(what, dy, y, w, groups, stride, pad, Lin):
+    if dy.dim() != 3 or w.dim() != 3 or not dy.is_contiguous() or not w.is_contiguous():
+        raise ValueError(f"{what}: dy must be contiguous [B][Co][Lout] and w contiguous [Co][Ci / groups][K]")
+    if y is not None and (tuple(y.shape) != tuple(dy.shape) or not y.is_contiguous()):
+        raise ValueError(f"{what}: the stored output must have dy's shape {tuple(dy.shape)}")
+    B, Co, Lout = dy.shape
+    if w.shape[0] != Co or Co % groups:
+        raise ValueError(f"{what}: weight {tuple(w.shape)} against dy {tuple(dy.shape)} in {groups} groups")
+    Ci, K = w.shape[1] * groups, w.shape[2]
+    if Lin + 2 * pad < K or (Lin + 2 * pad - K) // stride + 1 != Lout:
+        raise ValueError(f"{what}: Lin = {Lin} does not give Lout = {Lout} (k {K}, stride {stride}, pad {pad})")
+    return B, Ci, Co, Lout, K
+
+
+def conv_bwd_data(dy, y, w, Lin, stride=1, pad=0, groups=1, slope=0.1, out=None):
+    """dx [B][Ci][Lin] of a Conv1d with weight w [Co][Ci / groups][K] from dy [B][Co][Lout] and the stored output y of the
+    layer that produced dy (LeakyReLU factor taken on load; None: no activation) (rvc_conv_bwd_data)."""
+    B, Ci, Co, Lout, K = _bwd_shapes("conv_bwd_data", dy, y, w, groups, stride, pad, Lin)
+    if out is None:
+        out = torch.empty(B, Ci, Lin, device=dy.device, dtype=torch.float32)
+    elif out.numel() < B * Ci * Lin or not out.is_contiguous():
+        raise ValueError("conv_bwd_data: output buffer too small")
+    check(_lib.load().rvc_conv_bwd_data(_p(dy), _p(y), _p(w), _p(out), B, Ci, Co, Lin, Lout, K, stride, pad, groups,
+                                        slope, _stream()), "conv_bwd_data")
+    return out
+
+
+def conv_bwd_weight_work(B, Ci, Co, Lout, K, groups=1):
+    """Bytes of chunk partials rvc_conv_bwd_weight would like for this layer."""
+    n = _lib.load().rvc_conv_bwd_weight_work_bytes(B, Ci, Co, Lout, K, groups)
+    if n <= 0:
+        raise ValueError("conv_bwd_weight: bad sizes")
+    return n
+
+
+def conv_bwd_weight(dy, y, x, dW, db, stride=1, pad=0, groups=1, slope=0.1, scale=1.0, accumulate=False, period=0,
+                    work=None):
+    """dW [Co][Ci / groups][K] and db [Co] (+)= scale * the weight and bias gradient of a Conv1d from dy [B][Co][Lout],
+    the stored output y (as ``conv_bwd_data``) and the layer's input x [B][Ci][Lin]; ``period`` > 0: x is the signals
+    [S][t] as DiscriminatorP's first conv views them, B = S * period (rvc_conv_bwd_weight)."""
+    if not x.is_contiguous() or not dW.is_contiguous() or not db.is_contiguous():
+        raise ValueError("conv_bwd_weight: x, dW and db must be contiguous")
+    if period > 0:
+        if x.dim() != 2 or dy.dim() != 3 or x.shape[0] * period != dy.shape[0]:
+            raise ValueError(f"conv_bwd_weight: signals {tuple(x.shape)} at period {period} against dy {tuple(dy.shape)}")
+        t = x.shape[1]
+        Lin = (t + (period - t % period) % period) // period
+    else:
+        if x.dim() != 3 or dy.dim() != 3 or x.shape[0] != dy.shape[0] or x.shape[1] != dW.shape[1] * groups:
+            raise ValueError(f"conv_bwd_weight: x {tuple(x.shape)} against dy {tuple(dy.shape)}, dW {tuple(dW.shape)}")
+        t, Lin = 0, x.shape[2]
+    B, Ci, Co, Lout, K = _bwd_shapes("conv_bwd_weight", dy, y, dW, groups, stride, pad, Lin)
+    if db.numel() != Co:
+        raise ValueError("conv_bwd_weight: db must be [Co]")
+    if work is None:
+        work = torch.empty(conv_bwd_weight_work(B, Ci, Co, Lout, K, groups), device=dy.device, dtype=torch.uint8)
+    if work.numel() * work.element_size() < dW.numel() * 4:
+        raise ValueError("conv_bwd_weight: work buffer too small")
+    check(_lib.load().rvc_conv_bwd_weight(_p(dy), _p(y), _p(x), _p(dW), _p(db), B, Ci, Co, Lin, Lout, K, stride, pad,
+                                          groups, slope, scale, int(accumulate), period, t,
+                                          ctypes.c_void_p(work.data_ptr()), work.numel() * work.element_size(),
+                                          _stream()), "conv_bwd_weight")
+    return dW, db
+
+
+def wn_adamw(dW, db, v, g, bias, state, table, lr, betas, eps, weight_decay, step):
+    """Weight-norm backward, the rows' squared gradient norms into ``table`` [Co][3] (f64) and torch.optim.AdamW's
+    update of g, v and bias in place; ``state`` = (m_v, s_v, m_g, s_g, m_b, s_b), ``step`` counting from 1
+    (rvc_wn_adamw)."""
+    Co = g.numel()
+    n = v.numel() // Co
+    m_v, s_v, m_g, s_g, m_b, s_b = state
+    for a, size in ((dW, Co * n), (v, Co * n), (m_v, Co * n), (s_v, Co * n), (db, Co), (bias, Co), (m_g, Co), (s_g, Co),
+                    (m_b, Co), (s_b, Co), (g, Co)):
+        if a.numel() != size or not a.is_contiguous() or a.dtype != torch.float32:
+            raise ValueError(f"wn_adamw: a tensor of {a.numel()} values where {size} contiguous f32 belong")
+    if table.numel() < 3 * Co or not table.is_contiguous():
+        raise ValueError("wn_adamw: the table holds three values per row")
+    check(_lib.load().rvc_wn_adamw(_p(dW), _p(db), _p(v), _p(g), _p(bias), _p(m_v), _p(s_v), _p(m_g), _p(s_g), _p(m_b),
+                                   _p(s_b), Co, n, lr, betas[0], betas[1], eps, weight_decay, step, _pd64(table),
+                                   _stream()), "wn_adamw")
+
+
+def grad_norm(table, work=None):
+    """sqrt of the sum of an f64 table of squared norms -> device f64 [1] (rvc_grad_norm)."""
+    if not table.is_contiguous():
+        raise ValueError("grad_norm: table must be contiguous")
+    work, nb = (work, work.numel() * 8) if work is not None else disc_work(table.device)
+    out = torch.empty(1, device=table.device, dtype=torch.float64)
+    check(_lib.load().rvc_grad_norm(_pd64(table), table.numel(), _pd64(out), _pd64(work), nb, _stream()), "grad_norm")
+    return out
+
+
 SQRT = math.sqrt

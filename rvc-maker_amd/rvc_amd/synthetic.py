@@ -323,6 +323,30 @@ def make_disc_ckpt(version: str = "v2", seed: int = 1234) -> dict:
     return {"model": discriminator_state_dict(version, seed), "iteration": 1, "optimizer": {}, "learning_rate": 1e-4}
 
 
+OPT_STATE_STEP = 1000
+OPT_STATE_SCALE = 0.05  # the RMS of the seeded discriminators' gradients on the test signals lies between 5e-3 and 0.3
+
+
+def discriminator_optimizer_state(version: str = "v2", seed: int = 1234) -> dict:
+    """A warm ``torch.optim.AdamW`` state of ``net_d`` after ``OPT_STATE_STEP`` steps, in the layout of
+    ``optimizer.state_dict()`` (``{"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...]}``), parameter
+    i being the i-th key of ``discriminator_keys(version)`` -- ``net_d.parameters()``' order.  Every value is a NumPy
+    draw rounded to f32, so it regenerates bit for bit from the seed: ``exp_avg ~ N(0, 0.05)`` (the scale of the
+    gradients) and ``exp_avg_sq = 0.05^2 U(0.25, 4)``."""
+    from .discriminator import discriminator_keys
+    g = _Gen(seed ^ 0x0ADA)
+    state = {}
+    keys = discriminator_keys(version)
+    for i, shape in enumerate(keys.values()):
+        state[i] = {"step": torch.tensor(float(OPT_STATE_STEP)), "exp_avg": g.normal(shape, OPT_STATE_SCALE),
+                    "exp_avg_sq": g.uniform(shape, 0.25, 4.0) * float(OPT_STATE_SCALE ** 2)}
+    hps = train_config(40000, version)["train"]
+    group = {"lr": hps["learning_rate"], "betas": tuple(hps["betas"]), "eps": hps["eps"], "weight_decay": 0.01,
+             "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+             "fused": None, "params": list(range(len(keys)))}
+    return {"state": state, "param_groups": [group]}
+
+
 def write_train_experiment(exp_dir: str, sr: int = 40000, version: str = "v2", frames=(150, 150), seed: int = 1234,
                            sid: int = 3, with_d: bool = False) -> str:
     """A seeded experiment folder as the reference's preprocessing and extraction leave it: ``config.json``,

@@ -15,9 +15,9 @@ flow in the forward direction -- plus the linear and mel spectrograms (``train.p
                        first epoch (``train.py:377-393``).
 
 One utterance per call (B = 1, no padding): every mask of the reference is all ones, and its padded batch computes
-the same values on an utterance's valid frames.  No backward pass, no optimizer step (so both of the
-loop's ``net_d`` passes see the saved D), no AMP; the MRF-HiFi-GAN and RefineGAN decoders are refused
-here.  The kernels are csrc/trainfwd.hip and csrc/discriminator.hip; the encoder, flow, decoder and most of the
+the same values on an utterance's valid frames (DESIGN.md §18).  No generator backward pass or optimizer step, no AMP;
+without ``d_step`` both of the loop's ``net_d`` passes see the saved D, with it D takes its own step
+between them; the MRF-HiFi-GAN and RefineGAN decoders are refused here.  The kernels are csrc/trainfwd.hip and csrc/discriminator.hip; the encoder, flow, decoder and most of the
 discriminators' layers run on the conv engine as ``SynthesizerAMD`` does.
 """
 from __future__ import annotations
@@ -277,11 +277,17 @@ def generator_losses(model: TrainSynthAMD, phone, pitch, pitchf, spec, sid, cfg:
 D_LOSSES = ("loss_disc", "loss_gen", "loss_fm")  # the new per-utterance scalars, each aggregated as a plain mean
 
 
-def step_losses(model: TrainSynthAMD, disc, phone, pitch, pitchf, spec, wave, sid, cfg: dict = None, **draws) -> dict:
+def step_losses(model: TrainSynthAMD, disc, phone, pitch, pitchf, spec, wave, sid, cfg: dict = None, d_step: bool = False,
+                d_snapshot: dict = None, **draws) -> dict:
     """Every loss of one training step on one utterance (train.py:843-869): the forward, ``wave`` [T * hop] sliced at
     ``ids_slice * hop`` for ``segment_size`` samples (train.py:850), ``disc`` (a ``DiscriminatorAMD``) on that slice
     and ``y_hat`` -> ``DiscriminatorAMD.losses``' dict with ``loss_mel``, ``loss_kl`` and ``loss_gen_all`` (floats, one
-    host read).  ``loss_mel`` and ``loss_kl`` are the bits ``generator_losses`` returns for the same draws."""
+    host read).  ``loss_mel`` and ``loss_kl`` are the bits ``generator_losses`` returns for the same draws.
+
+    ``d_step`` (``disc`` a ``DiscriminatorTrainerAMD``): D takes its optimizer step on this pair between the two passes,
+    as the loop does (train.py:851-863) -- ``loss_disc`` and its lists are the first pass', ``loss_gen``, ``loss_fm`` and
+    ``loss_gen_all`` see the stepped D, ``grad_norm_d`` is added -- and D is put back (to ``d_snapshot``, or to what it
+    was on entry), so the numbers do not depend on what was scored before."""
     hps = cfg or model.hps
     y_hat, ids, (z, z_p, m_p, logs_p, m_q, logs_q) = model.forward(phone, pitch, pitchf, spec, sid, **draws)
     l1, kl = _losses(hps, spec, y_hat, ids, z_p, logs_q, m_p, logs_p)
@@ -289,8 +295,18 @@ def step_losses(model: TrainSynthAMD, disc, phone, pitch, pitchf, spec, wave, si
     wave = wave.reshape(-1)
     if st + seg > wave.numel():
         raise ValueError(f"step_losses: the wave has {wave.numel()} samples, the slice ends at {st + seg}")
-    return disc.losses(wave[st:st + seg].float().contiguous(), y_hat, l1, kl, float(hps["train"]["c_mel"]),
-                       float(hps["train"]["c_kl"]))
+    wave = wave[st:st + seg].float().contiguous()
+    c_mel, c_kl = float(hps["train"]["c_mel"]), float(hps["train"]["c_kl"])
+    if not d_step:
+        return disc.losses(wave, y_hat, l1, kl, c_mel, c_kl)
+    snap = d_snapshot if d_snapshot is not None else disc.snapshot()
+    try:
+        first = disc.step([(wave, y_hat)])
+        out = disc.losses(wave, y_hat, l1, kl, c_mel, c_kl)
+    finally:
+        disc.restore(snap)
+    out.update(first)
+    return out
 
 
 def aggregate_gan(per_utt: list) -> dict:
@@ -394,7 +410,7 @@ def _wave_of(wav_path, device):
 
 
 def evaluate(exp_dir: str, checkpoint, limit: int = None, seed: int = 0, device: str = "cuda",
-             vocoder: str = "Default", d_checkpoint=None) -> dict:
+             vocoder: str = "Default", d_checkpoint=None, d_step: bool = False) -> dict:
     """Score a generator checkpoint (a ``G_*.pth`` path, its loaded dict, or a built ``TrainSynthAMD``) on the
     utterances of ``exp_dir/filelist.txt``: per-utterance ``loss_mel`` / ``loss_kl`` and the aggregates one reference
     batch of them would log (``aggregate``).  Utterance i of the filelist draws from ``seed + i``, so its numbers do
@@ -402,8 +418,16 @@ def evaluate(exp_dir: str, checkpoint, limit: int = None, seed: int = 0, device:
 
     ``d_checkpoint`` (a ``D_*.pth`` path, its loaded dict, or a built ``DiscriminatorAMD``): the entries and the
     aggregates also carry ``loss_disc``, ``loss_gen``, ``loss_fm`` and ``loss_gen_all`` (``step_losses``,
-    ``aggregate_gan``), the entries the per-discriminator lists too.  Without it the result is what it always was."""
+    ``aggregate_gan``), the entries the per-discriminator lists too.  Without it the result is what it always was.
+
+    ``d_step`` (needs ``d_checkpoint``: a path, a dict or a built ``DiscriminatorTrainerAMD``): per utterance D takes
+    its optimizer step on that utterance's pair before ``loss_gen`` / ``loss_fm`` / ``loss_gen_all`` are taken, as the
+    training loop logs them (``step_losses``), the entries carry ``grad_norm_d``, and D is restored after each."""
+    if d_step and d_checkpoint is None:
+        raise ValueError("rvc_amd: d_step needs d_checkpoint (the D_*.pth whose step is taken)")
     hps = _load_hps(exp_dir)
+    if d_step and hps["train"].get("fp16_run"):
+        raise NotImplementedError("rvc_amd: fp16_run / AMP training: the discriminator's step on the device is f32")
     if isinstance(checkpoint, TrainSynthAMD):
         model = checkpoint
     else:
@@ -412,11 +436,15 @@ def evaluate(exp_dir: str, checkpoint, limit: int = None, seed: int = 0, device:
         model = TrainSynthAMD(ck, hps, device, vocoder=vocoder)
     disc = None
     if d_checkpoint is not None:
-        from .discriminator import DiscriminatorAMD
+        from .discriminator import DiscriminatorAMD, DiscriminatorTrainerAMD
         disc = d_checkpoint
         if not isinstance(disc, DiscriminatorAMD):
             dk = torch.load(disc, map_location="cpu", weights_only=False) if isinstance(disc, str) else disc
-            disc = DiscriminatorAMD(dk, model.version, device)
+            disc = DiscriminatorTrainerAMD(dk, model.version, hps["train"], device) if d_step else \
+                DiscriminatorAMD(dk, model.version, device)
+        elif d_step and not isinstance(disc, DiscriminatorTrainerAMD):
+            raise TypeError("rvc_amd: d_step needs a DiscriminatorTrainerAMD (a DiscriminatorAMD holds no optimizer)")
+    snap = disc.snapshot() if d_step else None
     rows = read_filelist(os.path.join(exp_dir, "filelist.txt"))
     if limit is not None:
         rows = rows[:limit]
@@ -434,11 +462,14 @@ def evaluate(exp_dir: str, checkpoint, limit: int = None, seed: int = 0, device:
         if disc is None:
             losses = generator_losses(model, *args, parse_sid(sid), hps, seed=seed + i)
         else:
-            losses = step_losses(model, disc, *args, _wave_of(wav, device), parse_sid(sid), hps, seed=seed + i)
+            extra = {"d_step": True, "d_snapshot": snap} if d_step else {}
+            losses = step_losses(model, disc, *args, _wave_of(wav, device), parse_sid(sid), hps, seed=seed + i, **extra)
         per_utt.append({"index": i, "wav": wav, "frames": T, **losses})
     out = aggregate(per_utt)
     if disc is not None:
         out.update(aggregate_gan(per_utt))
+    if d_step:
+        out["grad_norm_d"] = sum(u["grad_norm_d"] for u in per_utt) / len(per_utt) if per_utt else None
     out.update(utterances=per_utt, scored=len(per_utt), skipped=skipped)
     return out
 
@@ -451,19 +482,27 @@ def main(argv=None):
     ap.add_argument("--ckpt", required=True, action="append", help="G_*.pth (repeatable)")
     ap.add_argument("--d-ckpt", action="append", default=None,
                     help="D_*.pth, once per --ckpt and paired with them in order")
+    ap.add_argument("--d-step", action="store_true",
+                    help="step D on each utterance's pair before loss_gen / loss_fm, as the training loop logs them; "
+                         "adds grad_norm_d (needs --d-ckpt)")
     ap.add_argument("--limit", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda")
     a = ap.parse_args(argv)
     if a.d_ckpt is not None and len(a.d_ckpt) != len(a.ckpt):
         ap.error(f"--d-ckpt was given {len(a.d_ckpt)} times, --ckpt {len(a.ckpt)}: one D per G, in order")
+    if a.d_step and a.d_ckpt is None:
+        ap.error("--d-step requires --d-ckpt")
     for n, ck in enumerate(a.ckpt):
         dk = a.d_ckpt[n] if a.d_ckpt is not None else None
-        r = evaluate(a.exp, ck, a.limit, a.seed, a.device, d_checkpoint=dk)
+        extra = {"d_step": True} if a.d_step else {}
+        r = evaluate(a.exp, ck, a.limit, a.seed, a.device, d_checkpoint=dk, **extra)
         line = {"checkpoint": ck, "loss_mel": r["loss_mel"], "loss_kl": r["loss_kl"],
                 "scored": r["scored"], "skipped": r["skipped"]}
         if dk is not None:
             line.update(d_checkpoint=dk, **{k: r[k] for k in D_LOSSES + ("loss_gen_all",)})
+        if a.d_step:
+            line.update(grad_norm_d=r["grad_norm_d"])
         print(json.dumps(line), flush=True)
 
 

@@ -362,6 +362,9 @@ int rvc_adain(const float* x, const float* noise, const float* w, float* y, int6
  * img (bordered [Tp+2][M+2]) = BN(mel^T), frames reflect-padded to Tp     RMVPE.py:64,144,213
  * avgpool2 / interleave4 on bordered images                              RMVPE.py:35,93
  * img_to_seq: [C][H][W] image -> [C*W][H] sequence                       RMVPE.py:144
+ *        mel_image, avgpool2 and interleave4 write the zero border of the image they produce (interleave4: of its
+ *        C channels) as well as its interior: the output needs no zero fill.  One image per call; the f64 forms
+ *        below (the same kernels) take B images.
  * bigru: recurrence of nn.GRU(384, 256, bidirectional); gi = W_ih x + b_ih
  *        [2][768][T], whh [2][768][256], bhh [2][768], y [512][T];
  *        gran_ws: 8 KiB scratch (zeroed by the call), err: device int set to 1 when a step's hand-off wait
@@ -455,8 +458,8 @@ int rvc_wino64_conv(const rvc_wino64_args* a, void* ws, int64_t ws_bytes, rvc_st
 /* stft_mag64: rvc_stft_mag with the f64 magnitudes unrounded */
 int rvc_stft_mag64(const float* x, const float* win, double* mag, int64_t B, int64_t N, int64_t F, int nfft, int hop,
                    int64_t x_bstride, int64_t mag_bstride, rvc_stream_t stream);
-/* f64 forms of rvc_mel_image / avgpool2 / interleave4 / img_to_seq over B images (batch strides, 0 = dense
- * unused when B == 1); mel_image64 writes only the interior (the caller keeps the border zero). */
+/* f64 forms of rvc_mel_image / avgpool2 / interleave4 / img_to_seq (the same kernels) over B images (batch strides
+ * in elements, unused when B == 1); like them, the three that produce a bordered image write its zero border. */
 int rvc_mel_image64(const double* mel, double* img, int64_t B, int64_t M, int64_t F, int64_t Tp, double scale,
                     double shift, int64_t mel_bstride, int64_t img_bstride, rvc_stream_t stream);
 int rvc_avgpool2_64(const double* in, double* out, int64_t B, int64_t C, int64_t H, int64_t W, int64_t in_bstride,

@@ -138,101 +138,187 @@ extern "C" int rvc_stft_mag64(const float* x, const float* win, double* mag, int
     return stft_mag_launch<double>(x, win, mag, B, N, F, nfft, hop, x_bstride, mag_bstride, stream);
 }
 
-// ---------------------------------------------------------------- U-Net input image
-// img[(t+1)*(W+2) + m+1] = mel[m][src(t)] * scale + shift for t < Tp (reflect-padded frames,
-// RMVPE.py:213) with the encoder's input BatchNorm2d(1) folded to (scale, shift) (RMVPE.py:64).
-// The image border cells are left untouched (caller keeps them zero).
-__global__ void mel_image_kernel(const float* mel, float* img, int M, int64_t F, int64_t Tp, float scale,
-                                 float shift) {
-    int64_t t = (int64_t)blockIdx.x;
-    int m = threadIdx.x;
+// ---------------------------------------------------------------- U-Net image glue, f32 and f64
+// One kernel set for both arithmetics (T = float: the f32 form, one image per launch from the exported f32 entry
+// points; T = double: the f64 form, B images with batch strides).  Images are bordered [C][H+2][W+2]; each kernel
+// that writes one writes its zero border too, so no image needs a zero-fill launch before it.
+
+// the zero border cells beside interior cell (y, x) of a [H + 2][W + 2] plane (corners by the corner cells); a
+// plane with one interior row or column has that cell first and last at once
+template <typename T>
+RVC_DEV void border_zero(T* plane, int y, int x, int H, int W) {
+    const int R = W + 2;
+    if (x == 0) plane[(int64_t)(y + 1) * R] = T(0);
+    if (x == W - 1) plane[(int64_t)(y + 1) * R + W + 1] = T(0);
+    if (y == 0) {
+        plane[x + 1] = T(0);
+        if (x == 0) plane[0] = T(0);
+        if (x == W - 1) plane[W + 1] = T(0);
+    }
+    if (y == H - 1) {
+        T* row = plane + (int64_t)(H + 1) * R;
+        row[x + 1] = T(0);
+        if (x == 0) row[0] = T(0);
+        if (x == W - 1) row[W + 1] = T(0);
+    }
+}
+
+// img[(t+1)*(M+2) + m+1] = mel[m][src(t)] * scale + shift for t < Tp (reflect-padded frames, RMVPE.py:213) with
+// the encoder's input BatchNorm2d(1) folded to (scale, shift) (RMVPE.py:64)
+template <typename T>
+__global__ void mel_image_kernel(const T* mel, T* img, int M, int64_t F, int64_t Tp, T scale, T shift, int64_t mel_bs,
+                                 int64_t img_bs) {
+    const int64_t t = blockIdx.x;
+    const int m = threadIdx.x;
+    mel += blockIdx.y * mel_bs;
+    img += blockIdx.y * img_bs;
     if (t >= Tp || m >= M) return;
-    int64_t s = t < F ? t : 2 * (F - 1) - t;
+    const int64_t s = t < F ? t : 2 * (F - 1) - t;
     img[(t + 1) * (M + 2) + m + 1] = mel[(int64_t)m * F + s] * scale + shift;
+    border_zero(img, (int)t, m, (int)Tp, M);
 }
 
-extern "C" int rvc_mel_image(const float* mel, float* img, int64_t M, int64_t F, int64_t Tp, float scale, float shift,
-                             rvc_stream_t stream) {
-    RVC_CHECK_ARG(mel && img && M > 0 && M <= 1024 && F > 1 && Tp >= F && Tp - F < F, "mel_image: bad args");
-    hipLaunchKernelGGL(mel_image_kernel, dim3((unsigned)Tp), dim3((unsigned)((M + 63) / 64 * 64)), 0,
-                       (hipStream_t)stream, mel, img, (int)M, F, Tp, scale, shift);
-    RVC_HIP(hipGetLastError());
-    return RVC_OK;
-}
-
-// ---------------------------------------------------------------- AvgPool2d(2) on bordered images
-// in [C][H+2][W+2] -> out [C][H/2+2][W/2+2]; ((a + b) + c) + d then / 4 as torch's CPU kernel.
-__global__ void avgpool2_kernel(const float* in, float* out, int C, int H, int W) {
+// AvgPool2d(2): in [C][H+2][W+2] -> out [C][H/2+2][W/2+2]; ((a + b) + c) + d then / 4 as torch's CPU kernel
+template <typename T>
+__global__ void avgpool2_kernel(const T* in, T* out, int C, int H, int W, int64_t in_bs, int64_t out_bs) {
     const int Ho = H / 2, Wo = W / 2;
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t n = (int64_t)C * Ho * Wo;
-    if (i >= n) return;
-    int x = (int)(i % Wo);
-    int64_t r = i / Wo;
-    int y = (int)(r % Ho);
-    int c = (int)(r / Ho);
-    const float* ib = in + (int64_t)c * (H + 2) * (W + 2);
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    in += blockIdx.y * in_bs;
+    out += blockIdx.y * out_bs;
+    if (i >= (int64_t)C * Ho * Wo) return;
+    const int x = (int)(i % Wo);
+    const int64_t r = i / Wo;
+    const int y = (int)(r % Ho), c = (int)(r / Ho);
+    const T* ib = in + (int64_t)c * (H + 2) * (W + 2);
     const int64_t a0 = (int64_t)(2 * y + 1) * (W + 2) + 2 * x + 1;
-    float s = ib[a0];
+    T s = ib[a0];
     s += ib[a0 + 1];
     s += ib[a0 + W + 2];
     s += ib[a0 + W + 3];
-    out[(int64_t)c * (Ho + 2) * (Wo + 2) + (int64_t)(y + 1) * (Wo + 2) + x + 1] = s / 4.0f;
+    out[(int64_t)c * (Ho + 2) * (Wo + 2) + (int64_t)(y + 1) * (Wo + 2) + x + 1] = s / T(4);
+    border_zero(out + (int64_t)c * (Ho + 2) * (Wo + 2), y, x, Ho, Wo);
 }
 
-extern "C" int rvc_avgpool2(const float* in, float* out, int64_t C, int64_t H, int64_t W, rvc_stream_t stream) {
-    RVC_CHECK_ARG(in && out && C > 0 && H >= 2 && W >= 2, "avgpool2: bad args");
-    int64_t n = C * (H / 2) * (W / 2);
-    hipLaunchKernelGGL(avgpool2_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, in, out, (int)C, (int)H,
-                       (int)W);
+// ConvTranspose2d(3, s2, p1, op1) phases: ph[py*2+px] are [C][H+2][W+2] bordered (computed on the input grid by the
+// conv engine); out (bordered, [*][2H+2][2W+2], first C channels) gets out[c][2y+py][2x+px] = phase[c][y][x]
+template <typename T>
+__global__ void interleave4_kernel(const T* ph, T* out, int C, int H, int W, int64_t ph_bs, int64_t out_bs) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int Ho = 2 * H, Wo = 2 * W;
+    ph += blockIdx.y * ph_bs;
+    out += blockIdx.y * out_bs;
+    if (i >= (int64_t)C * Ho * Wo) return;
+    const int xo = (int)(i % Wo);
+    const int64_t r = i / Wo;
+    const int yo = (int)(r % Ho), c = (int)(r / Ho);
+    const int py = yo & 1, px = xo & 1, y = yo >> 1, x = xo >> 1;
+    const int64_t plane = (int64_t)(H + 2) * (W + 2);
+    out[(int64_t)c * (Ho + 2) * (Wo + 2) + (int64_t)(yo + 1) * (Wo + 2) + xo + 1] =
+        ph[((int64_t)(py * 2 + px) * C + c) * plane + (int64_t)(y + 1) * (W + 2) + x + 1];
+    border_zero(out + (int64_t)c * (Ho + 2) * (Wo + 2), yo, xo, Ho, Wo);
+}
+
+// cnn output -> GRU input: x[c*W + f][t] = img[c][t+1][f+1]   (E2E.forward: .transpose(1, 2).flatten(-2), RMVPE.py:144)
+template <typename T>
+__global__ void img_to_seq_kernel(const T* img, T* x, int C, int64_t H, int W, int64_t img_bs, int64_t x_bs) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int cf = blockIdx.y;
+    img += blockIdx.z * img_bs;
+    x += blockIdx.z * x_bs;
+    if (t >= H) return;
+    const int c = cf / W, f = cf - c * W;
+    x[(int64_t)cf * H + t] = img[(int64_t)c * (H + 2) * (W + 2) + (t + 1) * (W + 2) + f + 1];
+}
+
+template <typename T>
+static int mel_image_launch(const T* mel, T* img, int64_t B, int64_t M, int64_t F, int64_t Tp, T scale, T shift,
+                            int64_t mel_bs, int64_t img_bs, rvc_stream_t stream) {
+    RVC_CHECK_ARG(mel && img && B > 0 && B < 65536 && M > 0 && M <= 1024 && F > 1 && Tp >= F && Tp - F < F &&
+                      Tp < (1ll << 31),
+                  "mel_image: bad args");
+    RVC_CHECK_ARG(B == 1 || (mel_bs >= M * F && img_bs >= (Tp + 2) * (M + 2)), "mel_image: bad strides");
+    hipLaunchKernelGGL(mel_image_kernel<T>, dim3((unsigned)Tp, (unsigned)B), dim3((unsigned)((M + 63) / 64 * 64)), 0,
+                       (hipStream_t)stream, mel, img, (int)M, F, Tp, scale, shift, mel_bs, img_bs);
     RVC_HIP(hipGetLastError());
     return RVC_OK;
 }
 
-// ---------------------------------------------------------------- ConvTranspose2d(3, s2, p1, op1) phases
-// phases[py*2+px] are [C][H+2][W+2] bordered (computed on the input grid by the conv engine);
-// out (bordered, [*][2H+2][2W+2], first C channels) gets out[c][2y+py][2x+px] = phase[c][y][x].
-__global__ void interleave4_kernel(const float* ph, float* out, int C, int H, int W) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int Ho = 2 * H, Wo = 2 * W;
-    int64_t n = (int64_t)C * Ho * Wo;
-    if (i >= n) return;
-    int xo = (int)(i % Wo);
-    int64_t r = i / Wo;
-    int yo = (int)(r % Ho);
-    int c = (int)(r / Ho);
-    int py = yo & 1, px = xo & 1, y = yo >> 1, x = xo >> 1;
-    const int64_t plane = (int64_t)(H + 2) * (W + 2);
-    float v = ph[((int64_t)(py * 2 + px) * C + c) * plane + (int64_t)(y + 1) * (W + 2) + x + 1];
-    out[(int64_t)c * (Ho + 2) * (Wo + 2) + (int64_t)(yo + 1) * (Wo + 2) + xo + 1] = v;
+template <typename T>
+static int avgpool2_launch(const T* in, T* out, int64_t B, int64_t C, int64_t H, int64_t W, int64_t in_bs,
+                           int64_t out_bs, rvc_stream_t stream) {
+    RVC_CHECK_ARG(in && out && B > 0 && B < 65536 && C > 0 && H >= 2 && W >= 2, "avgpool2: bad args");
+    RVC_CHECK_ARG(B == 1 || (in_bs >= C * (H + 2) * (W + 2) && out_bs >= C * (H / 2 + 2) * (W / 2 + 2)),
+                  "avgpool2: bad strides");
+    const int64_t n = C * (H / 2) * (W / 2);
+    hipLaunchKernelGGL(avgpool2_kernel<T>, dim3(cdiv(n, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, in, out,
+                       (int)C, (int)H, (int)W, in_bs, out_bs);
+    RVC_HIP(hipGetLastError());
+    return RVC_OK;
+}
+
+template <typename T>
+static int interleave4_launch(const T* phases, T* out, int64_t B, int64_t C, int64_t H, int64_t W, int64_t ph_bs,
+                              int64_t out_bs, rvc_stream_t stream) {
+    RVC_CHECK_ARG(phases && out && B > 0 && B < 65536 && C > 0 && H > 0 && W > 0, "interleave4: bad args");
+    RVC_CHECK_ARG(B == 1 || (ph_bs >= 4 * C * (H + 2) * (W + 2) && out_bs >= C * (2 * H + 2) * (2 * W + 2)),
+                  "interleave4: bad strides");
+    const int64_t n = C * 4 * H * W;
+    hipLaunchKernelGGL(interleave4_kernel<T>, dim3(cdiv(n, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       phases, out, (int)C, (int)H, (int)W, ph_bs, out_bs);
+    RVC_HIP(hipGetLastError());
+    return RVC_OK;
+}
+
+template <typename T>
+static int img_to_seq_launch(const T* img, T* x, int64_t B, int64_t C, int64_t H, int64_t W, int64_t img_bs,
+                             int64_t x_bs, rvc_stream_t stream) {
+    RVC_CHECK_ARG(img && x && B > 0 && B < 65536 && C > 0 && H > 0 && W > 0 && C * W < 65536, "img_to_seq: bad args");
+    RVC_CHECK_ARG(B == 1 || (img_bs >= C * (H + 2) * (W + 2) && x_bs >= C * W * H), "img_to_seq: bad strides");
+    hipLaunchKernelGGL(img_to_seq_kernel<T>, dim3(cdiv(H, 256), (unsigned)(C * W), (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, img, x, (int)C, H, (int)W, img_bs, x_bs);
+    RVC_HIP(hipGetLastError());
+    return RVC_OK;
+}
+
+// the f32 entry points: one image
+extern "C" int rvc_mel_image(const float* mel, float* img, int64_t M, int64_t F, int64_t Tp, float scale, float shift,
+                             rvc_stream_t stream) {
+    return mel_image_launch<float>(mel, img, 1, M, F, Tp, scale, shift, 0, 0, stream);
+}
+
+extern "C" int rvc_avgpool2(const float* in, float* out, int64_t C, int64_t H, int64_t W, rvc_stream_t stream) {
+    return avgpool2_launch<float>(in, out, 1, C, H, W, 0, 0, stream);
 }
 
 extern "C" int rvc_interleave4(const float* phases, float* out, int64_t C, int64_t H, int64_t W,
                                rvc_stream_t stream) {
-    RVC_CHECK_ARG(phases && out && C > 0 && H > 0 && W > 0, "interleave4: bad args");
-    int64_t n = C * 4 * H * W;
-    hipLaunchKernelGGL(interleave4_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, phases, out, (int)C,
-                       (int)H, (int)W);
-    RVC_HIP(hipGetLastError());
-    return RVC_OK;
-}
-
-// ---------------------------------------------------------------- cnn output -> GRU input
-// x[c*W + f][t] = img[c][t+1][f+1]   (E2E.forward: .transpose(1, 2).flatten(-2), RMVPE.py:144)
-__global__ void img_to_seq_kernel(const float* img, float* x, int C, int64_t H, int W) {
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int cf = blockIdx.y;
-    if (t >= H) return;
-    int c = cf / W, f = cf - c * W;
-    x[(int64_t)cf * H + t] = img[(int64_t)c * (H + 2) * (W + 2) + (t + 1) * (W + 2) + f + 1];
+    return interleave4_launch<float>(phases, out, 1, C, H, W, 0, 0, stream);
 }
 
 extern "C" int rvc_img_to_seq(const float* img, float* x, int64_t C, int64_t H, int64_t W, rvc_stream_t stream) {
-    RVC_CHECK_ARG(img && x && C > 0 && H > 0 && W > 0, "img_to_seq: bad args");
-    hipLaunchKernelGGL(img_to_seq_kernel, dim3(cdiv(H, 256), (unsigned)(C * W)), dim3(256), 0, (hipStream_t)stream,
-                       img, x, (int)C, H, (int)W);
-    RVC_HIP(hipGetLastError());
-    return RVC_OK;
+    return img_to_seq_launch<float>(img, x, 1, C, H, W, 0, 0, stream);
+}
+
+// the f64 entry points: B images, batch strides in elements (unused when B == 1)
+extern "C" int rvc_mel_image64(const double* mel, double* img, int64_t B, int64_t M, int64_t F, int64_t Tp,
+                               double scale, double shift, int64_t mel_bstride, int64_t img_bstride,
+                               rvc_stream_t stream) {
+    return mel_image_launch<double>(mel, img, B, M, F, Tp, scale, shift, mel_bstride, img_bstride, stream);
+}
+
+extern "C" int rvc_avgpool2_64(const double* in, double* out, int64_t B, int64_t C, int64_t H, int64_t W,
+                               int64_t in_bstride, int64_t out_bstride, rvc_stream_t stream) {
+    return avgpool2_launch<double>(in, out, B, C, H, W, in_bstride, out_bstride, stream);
+}
+
+extern "C" int rvc_interleave4_64(const double* phases, double* out, int64_t B, int64_t C, int64_t H, int64_t W,
+                                  int64_t ph_bstride, int64_t out_bstride, rvc_stream_t stream) {
+    return interleave4_launch<double>(phases, out, B, C, H, W, ph_bstride, out_bstride, stream);
+}
+
+extern "C" int rvc_img_to_seq64(const double* img, double* x, int64_t B, int64_t C, int64_t H, int64_t W,
+                                int64_t img_bstride, int64_t x_bstride, rvc_stream_t stream) {
+    return img_to_seq_launch<double>(img, x, B, C, H, W, img_bstride, x_bstride, stream);
 }
 
 // ---------------------------------------------------------------- bidirectional GRU recurrence

@@ -3,7 +3,8 @@
 // top two bins closer than any f32 evaluation of the network resolves (3.2e-6 apart on the headline clip, while
 // f32 evaluations -- the reference's own at other thread counts among them -- err by up to 1.7e-4).  So the
 // whole network runs in f64 here: mel (f64 STFT, f64 mel GEMM + log), the U-Net convs on the f64 matrix cores
-// (v_mfma_f64_16x16x4_f64), pooling / transposed-conv phases / image->sequence in f64, W_ih, the BiGRU
+// (v_mfma_f64_16x16x4_f64), pooling / transposed-conv phases / image->sequence in f64 (rmvpe.hip's glue kernels,
+// one set for both arithmetics), W_ih, the BiGRU
 // recurrence and the classifier in f64; only the salience is rounded to f32, once, for the decode (which is
 // what the reference decodes: RMVPE.py:217).  Against the exact model the salience then errs by ~1e-13 and the
 // only remaining difference is the f32 input rounding the reference itself applies (RMVPE.py:224: <= 1.4e-7 on
@@ -589,92 +590,6 @@ int plan64(const rvc_conv64_args* a, C64& p, int& tile, dim3& grid, size_t& lds)
     grid = dim3(cdiv(p.nout, BN), (unsigned)((a->Co + BM - 1) / BM), (unsigned)(a->B * p.ksplit));
     RVC_CHECK_ARG(grid.y < 65536 && grid.z < 65536, "conv64: grid too large");
     return RVC_OK;
-}
-
-// ---------------------------------------------------------------- f64 image / sequence glue (rmvpe.hip's f32 forms)
-__global__ void mel_image64_kernel(const double* mel, double* img, int M, int64_t F, int64_t Tp, double scale,
-                                   double shift, int64_t mel_bs, int64_t img_bs) {
-    const int64_t t = blockIdx.x;
-    const int m = threadIdx.x;
-    mel += blockIdx.y * mel_bs;
-    img += blockIdx.y * img_bs;
-    if (t >= Tp || m >= M) return;
-    const int64_t s = t < F ? t : 2 * (F - 1) - t;
-    img[(t + 1) * (M + 2) + m + 1] = mel[(int64_t)m * F + s] * scale + shift;
-    // the zero border too (the image needs no zero-fill launch before it)
-    if (m == 0) {
-        img[(t + 1) * (M + 2)] = 0.0;
-        img[(t + 1) * (M + 2) + M + 1] = 0.0;
-    }
-    if (t == 0 || t == Tp - 1) {
-        double* row = img + (t == 0 ? 0 : (Tp + 1) * (M + 2));
-        row[m + 1] = 0.0;
-        if (m == 0) {
-            row[0] = 0.0;
-            row[M + 1] = 0.0;
-        }
-    }
-}
-
-// the zero border cells beside interior cell (y, x) of a [H + 2][W + 2] plane (corners by the corner cells)
-RVC_DEV void border_zero64(double* plane, int y, int x, int H, int W) {
-    const int R = W + 2;
-    if (x == 0) plane[(int64_t)(y + 1) * R] = 0.0;
-    if (x == W - 1) plane[(int64_t)(y + 1) * R + W + 1] = 0.0;
-    if (y == 0 || y == H - 1) {
-        double* row = plane + (y == 0 ? 0 : (int64_t)(H + 1) * R);
-        row[x + 1] = 0.0;
-        if (x == 0) row[0] = 0.0;
-        if (x == W - 1) row[W + 1] = 0.0;
-    }
-}
-
-// AvgPool2d(2): ((a + b) + c) + d, / 4
-__global__ void avgpool2_64_kernel(const double* in, double* out, int C, int H, int W, int64_t in_bs, int64_t out_bs) {
-    const int Ho = H / 2, Wo = W / 2;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    in += blockIdx.y * in_bs;
-    out += blockIdx.y * out_bs;
-    if (i >= (int64_t)C * Ho * Wo) return;
-    const int x = (int)(i % Wo);
-    const int64_t r = i / Wo;
-    const int y = (int)(r % Ho), c = (int)(r / Ho);
-    const double* ib = in + (int64_t)c * (H + 2) * (W + 2);
-    const int64_t a0 = (int64_t)(2 * y + 1) * (W + 2) + 2 * x + 1;
-    double s = ib[a0];
-    s += ib[a0 + 1];
-    s += ib[a0 + W + 2];
-    s += ib[a0 + W + 3];
-    out[(int64_t)c * (Ho + 2) * (Wo + 2) + (int64_t)(y + 1) * (Wo + 2) + x + 1] = s / 4.0;
-    border_zero64(out + (int64_t)c * (Ho + 2) * (Wo + 2), y, x, Ho, Wo);
-}
-
-__global__ void interleave4_64_kernel(const double* ph, double* out, int C, int H, int W, int64_t ph_bs,
-                                      int64_t out_bs) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int Ho = 2 * H, Wo = 2 * W;
-    ph += blockIdx.y * ph_bs;
-    out += blockIdx.y * out_bs;
-    if (i >= (int64_t)C * Ho * Wo) return;
-    const int xo = (int)(i % Wo);
-    const int64_t r = i / Wo;
-    const int yo = (int)(r % Ho), c = (int)(r / Ho);
-    const int py = yo & 1, px = xo & 1, y = yo >> 1, x = xo >> 1;
-    const int64_t plane = (int64_t)(H + 2) * (W + 2);
-    out[(int64_t)c * (Ho + 2) * (Wo + 2) + (int64_t)(yo + 1) * (Wo + 2) + xo + 1] =
-        ph[((int64_t)(py * 2 + px) * C + c) * plane + (int64_t)(y + 1) * (W + 2) + x + 1];
-    border_zero64(out + (int64_t)c * (Ho + 2) * (Wo + 2), yo, xo, Ho, Wo);
-}
-
-__global__ void img_to_seq64_kernel(const double* img, double* x, int C, int64_t H, int W, int64_t img_bs,
-                                    int64_t x_bs) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int cf = blockIdx.y;
-    img += blockIdx.z * img_bs;
-    x += blockIdx.z * x_bs;
-    if (t >= H) return;
-    const int c = cf / W, f = cf - c * W;
-    x[(int64_t)cf * H + t] = img[(int64_t)c * (H + 2) * (W + 2) + (t + 1) * (W + 2) + f + 1];
 }
 
 // ---------------------------------------------------------------- f64 Winograd F(4x4, 3x3) for the deep U-Net levels
@@ -1335,52 +1250,6 @@ extern "C" int rvc_conv64(const rvc_conv64_args* a, void* ws, int64_t ws_bytes, 
                            s, p);
         RVC_HIP(hipGetLastError());
     }
-    return RVC_OK;
-}
-
-extern "C" int rvc_mel_image64(const double* mel, double* img, int64_t B, int64_t M, int64_t F, int64_t Tp,
-                               double scale, double shift, int64_t mel_bstride, int64_t img_bstride,
-                               rvc_stream_t stream) {
-    RVC_CHECK_ARG(mel && img && B > 0 && M > 0 && M <= 1024 && F > 1 && Tp >= F && Tp - F < F, "mel_image64: bad args");
-    RVC_CHECK_ARG(B == 1 || (mel_bstride >= M * F && img_bstride >= (Tp + 2) * (M + 2)), "mel_image64: bad strides");
-    hipLaunchKernelGGL(mel_image64_kernel, dim3((unsigned)Tp, (unsigned)B), dim3((unsigned)((M + 63) / 64 * 64)), 0,
-                       (hipStream_t)stream, mel, img, (int)M, F, Tp, scale, shift, mel_bstride, img_bstride);
-    RVC_HIP(hipGetLastError());
-    return RVC_OK;
-}
-
-extern "C" int rvc_avgpool2_64(const double* in, double* out, int64_t B, int64_t C, int64_t H, int64_t W,
-                               int64_t in_bstride, int64_t out_bstride, rvc_stream_t stream) {
-    RVC_CHECK_ARG(in && out && B > 0 && C > 0 && H >= 2 && W >= 2, "avgpool2_64: bad args");
-    RVC_CHECK_ARG(B == 1 || (in_bstride >= C * (H + 2) * (W + 2) && out_bstride >= C * (H / 2 + 2) * (W / 2 + 2)),
-                  "avgpool2_64: bad strides");
-    const int64_t n = C * (H / 2) * (W / 2);
-    hipLaunchKernelGGL(avgpool2_64_kernel, dim3(cdiv(n, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, in, out,
-                       (int)C, (int)H, (int)W, in_bstride, out_bstride);
-    RVC_HIP(hipGetLastError());
-    return RVC_OK;
-}
-
-extern "C" int rvc_interleave4_64(const double* phases, double* out, int64_t B, int64_t C, int64_t H, int64_t W,
-                                  int64_t ph_bstride, int64_t out_bstride, rvc_stream_t stream) {
-    RVC_CHECK_ARG(phases && out && B > 0 && C > 0 && H > 0 && W > 0, "interleave4_64: bad args");
-    RVC_CHECK_ARG(B == 1 || (ph_bstride >= 4 * C * (H + 2) * (W + 2) && out_bstride >= C * (2 * H + 2) * (2 * W + 2)),
-                  "interleave4_64: bad strides");
-    const int64_t n = C * 4 * H * W;
-    hipLaunchKernelGGL(interleave4_64_kernel, dim3(cdiv(n, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                       phases, out, (int)C, (int)H, (int)W, ph_bstride, out_bstride);
-    RVC_HIP(hipGetLastError());
-    return RVC_OK;
-}
-
-extern "C" int rvc_img_to_seq64(const double* img, double* x, int64_t B, int64_t C, int64_t H, int64_t W,
-                                int64_t img_bstride, int64_t x_bstride, rvc_stream_t stream) {
-    RVC_CHECK_ARG(img && x && B > 0 && B < 65536 && C > 0 && H > 0 && W > 0, "img_to_seq64: bad args");
-    RVC_CHECK_ARG(B == 1 || (img_bstride >= C * (H + 2) * (W + 2) && x_bstride >= C * W * H),
-                  "img_to_seq64: bad strides");
-    hipLaunchKernelGGL(img_to_seq64_kernel, dim3(cdiv(H, 256), (unsigned)(C * W), (unsigned)B), dim3(256), 0,
-                       (hipStream_t)stream, img, x, (int)C, H, (int)W, img_bstride, x_bstride);
-    RVC_HIP(hipGetLastError());
     return RVC_OK;
 }
 

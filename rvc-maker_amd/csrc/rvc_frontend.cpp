@@ -26,20 +26,36 @@ struct W64 {
     double* v = nullptr;  // the Winograd F(4x4, 3x3) weights [36][Ci][Co] (rvc_wino64_use), else null
 };
 
+// RMVPE is one network in two arithmetics, T = float (ConvW weights, the split-operand engine at the context's
+// rm_prec) or double (W64 weights, rmvpe64.hip)
+template <typename T> struct WeightOf;
+template <> struct WeightOf<float> { using type = ConvW; };
+template <> struct WeightOf<double> { using type = W64; };
+template <typename T> using Wt = typename WeightOf<T>::type;
+
 // ConvBlockRes (RMVPE.py:11-44) with BatchNorm folded: conv.0 -> ReLU, conv.3 -> ReLU + shortcut
-// (c* for the f32 form, d* for the f64 form: one of the two sets is loaded)
+template <typename T>
 struct Cbr {
-    ConvW c0, c3, sc;
-    W64 d0, d3, dsc;
+    Wt<T> c0, c3, sc;
     bool has_sc = false;
 };
 
+template <typename T>
 struct ConvT2d {  // ConvTranspose2d(3, stride 2, pad 1, out pad 1) + BN + ReLU as 4 phase convs
-    ConvW ph[4];
-    W64 ph64[4];
+    Wt<T> ph[4];
     int ntap[4];
     int dy[4][4], dx[4][4];
     int64_t Co = 0;
+};
+
+template <typename T>
+struct RmNet {
+    Wt<T> mel, cnn, w_ih, fc;
+    T in_scale = 1, in_shift = 0;
+    T *w_hh = nullptr, *b_hh = nullptr;
+    std::vector<std::vector<Cbr<T>>> enc, inter;  // [level][block]
+    std::vector<ConvT2d<T>> dec_t;
+    std::vector<std::vector<Cbr<T>>> dec;
 };
 
 }  // namespace fem
@@ -52,16 +68,10 @@ struct ContentVec : ModelBase {
 };
 
 struct Rmvpe : ModelBase {
-    bool f64 = true;  // the f64 network (rmvpe64.hip) or the f32 one at the context's rm_prec
-    ConvW mel, cnn, w_ih, fc;
-    fem::W64 mel64, cnn64, w_ih64, fc64;
-    float in_scale = 1.f, in_shift = 0.f;
-    double in_scale64 = 1.0, in_shift64 = 0.0;
-    float *window = nullptr, *w_hh = nullptr, *b_hh = nullptr;
-    double *w_hh64 = nullptr, *b_hh64 = nullptr;
-    std::vector<std::vector<fem::Cbr>> enc, inter;  // [level][block]
-    std::vector<fem::ConvT2d> dec_t;
-    std::vector<std::vector<fem::Cbr>> dec;
+    bool f64 = true;  // which of the two is loaded: the f64 network or the f32 one at the context's rm_prec
+    fem::RmNet<float> n32;
+    fem::RmNet<double> n64;
+    float* window = nullptr;
     void* gran = nullptr;
     int* err = nullptr;
 };
@@ -237,9 +247,16 @@ int upload64(ModelBase& m, const std::vector<double>& h, double** out) {
     return RVC_OK;
 }
 
-// f64 KM weights from w laid out [Co][Ci][K] (times scale[co] in f64 when given) + an f64 bias (ops.Conv64)
-int make_w64(Rmvpe& M, const HostT& w, int64_t Co, int64_t Ci, int K, const std::vector<double>* scale,
-             const std::vector<double>* bias, W64& cw) {
+std::vector<double> to_f64(const std::vector<float>& v) { return std::vector<double>(v.begin(), v.end()); }
+
+int upload_as(ModelBase& m, const std::vector<float>& h, float** out) { return upload(m, h, out); }
+int upload_as(ModelBase& m, const std::vector<float>& h, double** out) { return upload64(m, to_f64(h), out); }
+
+// make_w: a conv weight laid out [Co][Ci][K] (a 3x3 / 1x1 Conv2d's [Co][Ci][kh][kw] with K = kh*kw), times
+// scale[co] in f64 when given, plus a bias, as the arithmetic's KM weights.
+// f64: KM [Ci*K][Co] and an f64 bias (ops.Conv64)
+int make_w(rvc_ctx*, Rmvpe& M, const HostT& w, int64_t Co, int64_t Ci, int K, const std::vector<double>* scale,
+           const std::vector<double>* bias, W64& cw) {
     MCHECK((int64_t)w.v.size() == Co * Ci * K, "rvc_load_rmvpe: weight of %zu values, expected %lld x %lld x %d",
            w.v.size(), (long long)Co, (long long)Ci, K);
     cw.Co = Co;
@@ -266,54 +283,54 @@ int make_w64(Rmvpe& M, const HostT& w, int64_t Co, int64_t Ci, int K, const std:
     return RVC_OK;
 }
 
-std::vector<double> to_f64(const std::vector<float>& v) { return std::vector<double>(v.begin(), v.end()); }
-
-// 3x3 / 1x1 Conv2d weight [Co][Ci][kh][kw] (optionally scaled per output channel) as a K = kh*kw conv
-int make_conv2d(rvc_ctx* c, Rmvpe& M, const HostT& w, const std::vector<double>* scale, const std::vector<float>& bias,
-                ConvW& cw) {
-    HostT w3;
-    w3.shape = {w.dim(0), w.dim(1), w.dim(2) * w.dim(3)};
+// f32: the scaled weight and the bias rounded to f32 once, then make_conv
+int make_w(rvc_ctx* c, Rmvpe& M, const HostT& w, int64_t Co, int64_t Ci, int K, const std::vector<double>* scale,
+           const std::vector<double>* bias, ConvW& cw) {
+    MCHECK((int64_t)w.v.size() == Co * Ci * K, "rvc_load_rmvpe: weight of %zu values, expected %lld x %lld x %d",
+           w.v.size(), (long long)Co, (long long)Ci, K);
+    HostT w3, b;
+    w3.shape = {Co, Ci, K};
     w3.v.resize(w.v.size());
-    const int64_t inner = (int64_t)w.v.size() / w.dim(0);
-    for (int64_t co = 0; co < w.dim(0); ++co)
+    const int64_t inner = Ci * K;
+    for (int64_t co = 0; co < Co; ++co)
         for (int64_t j = 0; j < inner; ++j)
             w3.v[co * inner + j] = scale ? (float)((double)w.v[co * inner + j] * (*scale)[co]) : w.v[co * inner + j];
-    HostT b;
-    b.v = bias;
-    b.shape = {(int64_t)bias.size()};
-    return make_conv(c, M, w3, &b, cw);
+    if (bias) {
+        b.v.assign(bias->begin(), bias->end());
+        b.shape = {(int64_t)bias->size()};
+    }
+    return make_conv(c, M, w3, bias ? &b : nullptr, cw);
 }
 
-int make_cbr(rvc_ctx* c, Rmvpe& M, Params& P, const std::string& p, Cbr& blk) {
+// a Conv2d weight [Co][Ci][kh][kw] with an f32 bias
+template <typename W>
+int make_conv2d(rvc_ctx* c, Rmvpe& M, const HostT& w, const std::vector<double>* scale, const std::vector<double>& bias,
+                W& cw) {
+    return make_w(c, M, w, w.dim(0), w.dim(1), (int)(w.dim(2) * w.dim(3)), scale, &bias, cw);
+}
+
+template <typename T>
+int make_cbr(rvc_ctx* c, Rmvpe& M, Params& P, const std::string& p, Cbr<T>& blk) {
     const char* convs[2][2] = {{"conv.0", "conv.1"}, {"conv.3", "conv.4"}};
     for (int i = 0; i < 2; ++i) {
         std::vector<double> s, t;
         MTRY(fold_bn(P, p + "." + convs[i][1], s, t));
         HostT w;
         MCHECK(P.get(p + "." + convs[i][0] + ".weight", w), "rvc_load_rmvpe: missing %s", P.missing.c_str());
-        if (M.f64) {
-            MTRY(make_w64(M, w, w.dim(0), w.dim(1), (int)(w.dim(2) * w.dim(3)), &s, &t, i == 0 ? blk.d0 : blk.d3));
-        } else {
-            std::vector<float> bf(t.begin(), t.end());
-            MTRY(make_conv2d(c, M, w, &s, bf, i == 0 ? blk.c0 : blk.c3));
-        }
+        MTRY(make_conv2d(c, M, w, &s, t, i == 0 ? blk.c0 : blk.c3));
     }
     if (P.has(p + ".shortcut.weight")) {
         HostT w, b;
         MCHECK(P.get(p + ".shortcut.weight", w) && P.get(p + ".shortcut.bias", b), "rvc_load_rmvpe: missing %s",
                P.missing.c_str());
-        if (M.f64) {
-            const std::vector<double> bd = to_f64(b.v);
-            MTRY(make_w64(M, w, w.dim(0), w.dim(1), (int)(w.dim(2) * w.dim(3)), nullptr, &bd, blk.dsc));
-        } else {
-            MTRY(make_conv2d(c, M, w, nullptr, b.v, blk.sc));
-        }
+        MTRY(make_conv2d(c, M, w, nullptr, to_f64(b.v), blk.sc));
         blk.has_sc = true;
     }
     return RVC_OK;
 }
 
-int make_convT2d(rvc_ctx* c, Rmvpe& M, Params& P, const std::string& p, ConvT2d& ct) {
+template <typename T>
+int make_convT2d(rvc_ctx* c, Rmvpe& M, Params& P, const std::string& p, ConvT2d<T>& ct) {
     std::vector<double> s, t;
     MTRY(fold_bn(P, p + ".conv1.1", s, t));
     HostT w;
@@ -322,15 +339,13 @@ int make_convT2d(rvc_ctx* c, Rmvpe& M, Params& P, const std::string& p, ConvT2d&
     ct.Co = Co;
     // per output parity: (kernel index, source offset) -- rmvpe.py _ConvT2d.TAPS
     const int tk[2][2] = {{1, -1}, {0, 2}}, td[2][2] = {{0, 0}, {1, 0}}, tn[2] = {1, 2};
-    HostT bias;
-    bias.v.assign(t.begin(), t.end());
-    bias.shape = {Co};
     int ph = 0;
     for (int py = 0; py < 2; ++py)
         for (int px = 0; px < 2; ++px, ++ph) {
             int n = 0;
             const int nt = tn[py] * tn[px];
-            std::vector<double> wd((size_t)Co * Ci * nt);  // [Co][Ci][ntap], BN scale folded in f64
+            HostT wp;  // the phase's taps [Co][Ci][ntap]; make_w folds the BN scale in f64
+            wp.v.resize((size_t)Co * Ci * nt);
             for (int a = 0; a < tn[py]; ++a)
                 for (int b2 = 0; b2 < tn[px]; ++b2, ++n) {
                     const int ky = tk[py][a], kx = tk[px][b2];
@@ -338,171 +353,65 @@ int make_convT2d(rvc_ctx* c, Rmvpe& M, Params& P, const std::string& p, ConvT2d&
                     ct.dx[ph][n] = td[px][b2];
                     for (int64_t co = 0; co < Co; ++co)
                         for (int64_t ci = 0; ci < Ci; ++ci)
-                            wd[(co * Ci + ci) * nt + n] = (double)w.v[((ci * Co + co) * 3 + ky) * 3 + kx] * s[co];
+                            wp.v[(co * Ci + ci) * nt + n] = w.v[((ci * Co + co) * 3 + ky) * 3 + kx];
                 }
             ct.ntap[ph] = nt;
-            if (M.f64) {
-                W64& cw = ct.ph64[ph];
-                cw.Co = Co;
-                cw.Ci = Ci;
-                cw.K = nt;
-                std::vector<double> km((size_t)Co * Ci * nt);
-                for (int64_t co = 0; co < Co; ++co)
-                    for (int64_t ci = 0; ci < Ci; ++ci)
-                        for (int q = 0; q < nt; ++q) km[(ci * nt + q) * Co + co] = wd[(co * Ci + ci) * nt + q];
-                MTRY(upload64(M, km, &cw.w));
-                MTRY(upload64(M, t, &cw.b));
-            } else {
-                HostT wp;
-                wp.shape = {Co, Ci, nt};
-                wp.v.resize(wd.size());
-                for (size_t i = 0; i < wd.size(); ++i) wp.v[i] = (float)wd[i];
-                MTRY(make_conv(c, M, wp, &bias, ct.ph[ph]));
-            }
+            MTRY(make_w(c, M, wp, Co, Ci, nt, &s, &t, ct.ph[ph]));
         }
     return RVC_OK;
 }
 
-// _Conv2d.__call__ on bordered [C][H+2][W+2] images
-int conv2d(rvc_ctx* c, Rmvpe& M, const ConvW& cw, const float* x, int64_t H, int64_t W, float* out, int out_act,
-           const float* res, hipStream_t s) {
-    const int64_t wrap = W + 2, L = (H + 2) * wrap;
-    CallOpts o;
-    o.Lout = L;
-    o.wrap = (int)wrap;
-    o.out_act = out_act;
-    o.res = res;
-    if (cw.K == 9) {
-        o.ntoff = 9;
-        for (int dy = 0; dy < 3; ++dy)
-            for (int dx = 0; dx < 3; ++dx) o.toff[dy * 3 + dx] = (int)(dy * wrap + dx);
-        o.pad = (int)(wrap + 1);
-    } else {
-        o.ntoff = 1;
-        o.toff[0] = 0;
-        o.pad = 0;
-    }
-    return conv(c, M, cw, x, L, out, o, s);
-}
-
-int cbr_run(rvc_ctx* c, Rmvpe& M, Scratch& sc, const Cbr& blk, const float* x, int64_t H, int64_t W, float* out,
-            hipStream_t s) {
-    const int64_t img = (H + 2) * (W + 2);
-    float* h = sc.take(blk.c0.Co * img);
-    RUN(conv2d(c, M, blk.c0, x, H, W, h, RVC_ACT_RELU, nullptr, s));
-    const float* res = x;
-    if (blk.has_sc) {
-        float* scb = sc.take(blk.c0.Co * img);
-        RUN(conv2d(c, M, blk.sc, x, H, W, scb, RVC_ACT_NONE, nullptr, s));
-        res = scb;
-    }
-    RUN(conv2d(c, M, blk.c3, h, H, W, out, RVC_ACT_RELU, res, s));
-    return RVC_OK;
-}
-
-// mel -> U-Net -> BiGRU -> fc for one sequence (rmvpe.py f0_device up to the decode)
-int rm_one(rvc_ctx* c, Rmvpe& M, Scratch& sc, const float* wav, int64_t N, float* sal, hipStream_t s) {
-    const int64_t F = 1 + N / kHop, Tp = 32 * ((F - 1) / 32 + 1);
-    // MelSpectrogram.forward (RMVPE.py:162-181): |STFT| in f64 (rvc_stft_mag), then the mel GEMM + log
-    float* mag = sc.take((int64_t)(kNfft / 2 + 1) * F);
-    RUN(rvc_stft_mag(wav, M.window, mag, 1, N, F, kNfft, kHop, 0, 0, s));
-    float* mel = sc.take((int64_t)kMels * F);
-    {
-        CallOpts o;
-        o.out_act = RVC_ACT_LOGCLAMP;
-        o.out_slope = 1e-5f;
-        RUN(conv(c, M, M.mel, mag, F, mel, o, s));
-    }
-    // mel2hidden input image (RMVPE.py:210-213)
-    int64_t H = Tp, W = kMels;
-    float* x = sc.take((H + 2) * (W + 2));
-    RUN(hipMemsetAsync(x, 0, (H + 2) * (W + 2) * 4, s) == hipSuccess ? RVC_OK : RVC_EHIP);
-    RUN(rvc_mel_image(mel, x, kMels, F, Tp, M.in_scale, M.in_shift, s));
-    // encoder (RMVPE.py:64-76): the last block of each level writes into the decoder's concat buffer
-    struct Cat {
-        float* buf;
-        int64_t C, H, W;
-    };
-    std::vector<Cat> cats;
-    int64_t C = M.enc[0][0].c0.Co;
-    const int nb = (int)M.enc[0].size();
-    for (size_t l = 0; l < M.enc.size(); ++l) {
-        const int64_t img = (H + 2) * (W + 2);
-        float* cat = sc.take(2 * C * img);
-        RUN(hipMemsetAsync(cat, 0, 2 * C * img * 4, s) == hipSuccess ? RVC_OK : RVC_EHIP);
-        for (int b = 0; b < nb; ++b) {
-            float* out = b == nb - 1 ? cat + C * img : sc.take(C * img);
-            MTRY(cbr_run(c, M, sc, M.enc[l][b], x, H, W, out, s));
-            x = out;
-        }
-        cats.push_back({cat, C, H, W});
-        float* pooled = sc.take(C * (H / 2 + 2) * (W / 2 + 2));
-        RUN(hipMemsetAsync(pooled, 0, C * (H / 2 + 2) * (W / 2 + 2) * 4, s) == hipSuccess ? RVC_OK : RVC_EHIP);
-        RUN(rvc_avgpool2(x, pooled, C, H, W, s));
-        x = pooled;
-        H /= 2;
-        W /= 2;
-        C *= 2;
-    }
-    for (auto& layer : M.inter)
-        for (auto& blk : layer) {
-            float* out = sc.take(blk.c0.Co * (H + 2) * (W + 2));
-            MTRY(cbr_run(c, M, sc, blk, x, H, W, out, s));
-            x = out;
-        }
-    // decoder (RMVPE.py:78-107)
-    for (size_t i = 0; i < M.dec_t.size(); ++i) {
-        const Cat& ct = cats[cats.size() - 1 - i];
-        const ConvT2d& T2 = M.dec_t[i];
-        const int64_t wrap = W + 2, Lc = (H + 2) * wrap;
-        float* ph = sc.take(4 * T2.Co * Lc);
-        for (int p = 0; p < 4; ++p) {
-            CallOpts o;
-            o.Lout = Lc;
-            o.wrap = (int)wrap;
-            o.out_act = RVC_ACT_RELU;
-            o.ntoff = T2.ntap[p];
-            for (int t = 0; t < T2.ntap[p]; ++t) o.toff[t] = (int)(T2.dy[p][t] * wrap + T2.dx[p][t]);
-            RUN(conv(c, M, T2.ph[p], x, Lc, ph + p * T2.Co * Lc, o, s));
-        }
-        RUN(rvc_interleave4(ph, ct.buf, T2.Co, H, W, s));
-        x = ct.buf;
-        H = ct.H;
-        W = ct.W;
-        for (auto& blk : M.dec[i]) {
-            float* out = sc.take(blk.c0.Co * (H + 2) * (W + 2));
-            MTRY(cbr_run(c, M, sc, blk, x, H, W, out, s));
-            x = out;
-        }
-    }
-    float* img = sc.take(3 * (H + 2) * (W + 2));
-    RUN(conv2d(c, M, M.cnn, x, H, W, img, RVC_ACT_NONE, nullptr, s));
-    float* seq = sc.take(3 * W * H);
-    RUN(rvc_img_to_seq(img, seq, 3, H, W, s));
-    // BiGRU + Linear + sigmoid (RMVPE.py:254-260, 141)
-    float* gi = sc.take(1536 * Tp);
-    {
-        CallOpts o;
-        RUN(conv(c, M, M.w_ih, seq, Tp, gi, o, s));
-    }
-    float* y = sc.take(512 * Tp);
-    RUN(rvc_bigru(gi, M.w_hh, M.b_hh, y, M.gran, M.err, Tp, s));
-    CallOpts o;
-    o.out_act = RVC_ACT_SIGMOID;
-    RUN(conv(c, M, M.fc, y, Tp, sal, o, s));
-    return RVC_OK;
-}
-
-// ------------------------------------------------------------------ the f64 network (rmvpe.py, precision "f64")
-struct C64Opts {
+// ------------------------------------------------------------------ RMVPE forward: the calls that differ by arithmetic
+// what rm_one asks of a conv: run_conv maps it to the f32 engine's arguments or the f64 engine's
+template <typename T>
+struct RmOpts {
     int64_t Lout = -1;
-    int pad = 0, out_act = RVC_ACT_NONE, y_f32 = 0, ntoff = 0, wrap = 0;
+    int pad = 0, out_act = RVC_ACT_NONE, ntoff = 0, wrap = 0;  // 2-D mode: tap offsets and border masking
     int toff[16] = {0};
-    double out_slope = 0.0;
-    const double* res = nullptr;
+    T out_slope = 0;
+    const T* res = nullptr;
 };
 
-int conv64(Rmvpe& M, const W64& cw, const double* x, int64_t Lin, void* y, const C64Opts& o, hipStream_t s) {
+int run_conv(rvc_ctx* c, Rmvpe& M, const ConvW& cw, const float* x, int64_t Lin, float* y, const RmOpts<float>& o,
+             hipStream_t s) {
+    CallOpts co;
+    co.Lout = o.Lout;
+    co.pad = o.pad;
+    co.out_act = o.out_act;
+    co.out_slope = o.out_slope;
+    co.res = o.res;
+    co.ntoff = o.ntoff;
+    co.wrap = o.wrap;
+    for (int i = 0; i < o.ntoff; ++i) co.toff[i] = o.toff[i];
+    return conv(c, M, cw, x, Lin, y, co, s);
+}
+
+// f64: Winograd for a 3x3 conv that has the transformed weights and an image large enough, else conv64; TO = float
+// rounds the output to f32 (the salience)
+template <typename TO>
+int run_conv(rvc_ctx*, Rmvpe& M, const W64& cw, const double* x, int64_t Lin, TO* y, const RmOpts<double>& o,
+             hipStream_t s) {
+    const int y_f32 = std::is_same<TO, float>::value;
+    const int64_t W = o.wrap - 2, H = o.wrap ? o.Lout / o.wrap - 2 : 0;
+    if (cw.v && o.ntoff == 9 && !y_f32 && rvc_wino64_use(cw.Ci, cw.Co, H, W)) {
+        rvc_wino64_args a;
+        memset(&a, 0, sizeof(a));
+        a.x = x;
+        a.v = cw.v;
+        a.bias = cw.b;
+        a.res = o.res;
+        a.y = y;
+        a.B = 1;
+        a.Ci = cw.Ci;
+        a.Co = cw.Co;
+        a.H = H;
+        a.W = W;
+        a.out_act = o.out_act;
+        const int64_t need = rvc_wino64_workspace_bytes(&a);
+        if (need < 0) return RVC_EINVAL;
+        MTRY(ensure_ws(M, need, s));
+        return rvc_wino64_conv(&a, M.ws, need, s);
+    }
     rvc_conv64_args a;
     memset(&a, 0, sizeof(a));
     a.x = x;
@@ -518,7 +427,7 @@ int conv64(Rmvpe& M, const W64& cw, const double* x, int64_t Lin, void* y, const
     a.K = cw.K;
     a.pad = o.pad;
     a.out_act = o.out_act;
-    a.y_f32 = o.y_f32;
+    a.y_f32 = y_f32;
     a.out_slope = o.out_slope;
     a.ntoff = o.ntoff;
     a.wrap = o.wrap;
@@ -529,145 +438,240 @@ int conv64(Rmvpe& M, const W64& cw, const double* x, int64_t Lin, void* y, const
     return rvc_conv64(&a, need ? M.ws : nullptr, need, s);
 }
 
-// _Conv2d.__call__ (f64) on bordered [C][H+2][W+2] images
-int conv2d64(Rmvpe& M, const W64& cw, const double* x, int64_t H, int64_t W, double* out, int out_act,
-             const double* res, hipStream_t s) {
-    if (cw.v && rvc_wino64_use(cw.Ci, cw.Co, H, W)) {
-        rvc_wino64_args a;
-        memset(&a, 0, sizeof(a));
-        a.x = x;
-        a.v = cw.v;
-        a.bias = cw.b;
-        a.res = res;
-        a.y = out;
-        a.B = 1;
-        a.Ci = cw.Ci;
-        a.Co = cw.Co;
-        a.H = H;
-        a.W = W;
-        a.out_act = out_act;
-        const int64_t need = rvc_wino64_workspace_bytes(&a);
-        if (need < 0) return RVC_EINVAL;
-        MTRY(ensure_ws(M, need, s));
-        return rvc_wino64_conv(&a, M.ws, need, s);
-    }
+int stft_mag(const float* x, const float* win, float* mag, int64_t N, int64_t F, hipStream_t s) {
+    return rvc_stft_mag(x, win, mag, 1, N, F, kNfft, kHop, 0, 0, s);
+}
+int stft_mag(const float* x, const float* win, double* mag, int64_t N, int64_t F, hipStream_t s) {
+    return rvc_stft_mag64(x, win, mag, 1, N, F, kNfft, kHop, 0, 0, s);
+}
+int mel_image(const float* mel, float* img, int64_t F, int64_t Tp, float sc, float sh, hipStream_t s) {
+    return rvc_mel_image(mel, img, kMels, F, Tp, sc, sh, s);
+}
+int mel_image(const double* mel, double* img, int64_t F, int64_t Tp, double sc, double sh, hipStream_t s) {
+    return rvc_mel_image64(mel, img, 1, kMels, F, Tp, sc, sh, 0, 0, s);
+}
+int avgpool2(const float* x, float* y, int64_t C, int64_t H, int64_t W, hipStream_t s) {
+    return rvc_avgpool2(x, y, C, H, W, s);
+}
+int avgpool2(const double* x, double* y, int64_t C, int64_t H, int64_t W, hipStream_t s) {
+    return rvc_avgpool2_64(x, y, 1, C, H, W, 0, 0, s);
+}
+int interleave4(const float* ph, float* y, int64_t C, int64_t H, int64_t W, hipStream_t s) {
+    return rvc_interleave4(ph, y, C, H, W, s);
+}
+int interleave4(const double* ph, double* y, int64_t C, int64_t H, int64_t W, hipStream_t s) {
+    return rvc_interleave4_64(ph, y, 1, C, H, W, 0, 0, s);
+}
+int img_to_seq(const float* img, float* x, int64_t C, int64_t H, int64_t W, hipStream_t s) {
+    return rvc_img_to_seq(img, x, C, H, W, s);
+}
+int img_to_seq(const double* img, double* x, int64_t C, int64_t H, int64_t W, hipStream_t s) {
+    return rvc_img_to_seq64(img, x, 1, C, H, W, 0, 0, s);
+}
+int bigru(Rmvpe& M, const float* gi, const float* whh, const float* bhh, float* y, int64_t T, hipStream_t s) {
+    return rvc_bigru(gi, whh, bhh, y, M.gran, M.err, T, s);
+}
+int bigru(Rmvpe& M, const double* gi, const double* whh, const double* bhh, double* y, int64_t T, hipStream_t s) {
+    return rvc_bigru64_batched(gi, 0, whh, bhh, y, 0, M.gran, M.err, 1, T, s);
+}
+
+template <typename T>
+T* take(Scratch& sc, int64_t n) {
+    return (T*)sc.take(n * (int64_t)(sizeof(T) / sizeof(float)));
+}
+
+// ------------------------------------------------------------------ RMVPE forward, one sequence
+// _Conv2d.__call__ on bordered [C][H+2][W+2] images: 3x3 (pad 1) or 1x1
+template <typename T>
+int conv2d(rvc_ctx* c, Rmvpe& M, const Wt<T>& cw, const T* x, int64_t H, int64_t W, T* out, int out_act, const T* res,
+           hipStream_t s) {
     const int64_t wrap = W + 2, L = (H + 2) * wrap;
-    C64Opts o;
+    RmOpts<T> o;
     o.Lout = L;
     o.wrap = (int)wrap;
     o.out_act = out_act;
     o.res = res;
+    o.ntoff = 1;
     if (cw.K == 9) {
         o.ntoff = 9;
         for (int dy = 0; dy < 3; ++dy)
             for (int dx = 0; dx < 3; ++dx) o.toff[dy * 3 + dx] = (int)(dy * wrap + dx);
         o.pad = (int)(wrap + 1);
-    } else {
-        o.ntoff = 1;
     }
-    return conv64(M, cw, x, L, out, o, s);
+    return run_conv(c, M, cw, x, L, out, o, s);
 }
 
-double* take64(Scratch& sc, int64_t n) { return (double*)sc.take(2 * n); }
-
-int cbr_run64(Rmvpe& M, Scratch& sc, const Cbr& blk, const double* x, int64_t H, int64_t W, double* out,
-              hipStream_t s) {
+template <typename T>
+int cbr_run(rvc_ctx* c, Rmvpe& M, Scratch& sc, const Cbr<T>& blk, const T* x, int64_t H, int64_t W, T* out,
+            hipStream_t s) {
     const int64_t img = (H + 2) * (W + 2);
-    double* h = take64(sc, blk.d0.Co * img);
-    RUN(conv2d64(M, blk.d0, x, H, W, h, RVC_ACT_RELU, nullptr, s));
-    const double* res = x;
+    T* h = take<T>(sc, blk.c0.Co * img);
+    RUN(conv2d<T>(c, M, blk.c0, x, H, W, h, RVC_ACT_RELU, nullptr, s));
+    const T* res = x;
     if (blk.has_sc) {
-        double* scb = take64(sc, blk.d0.Co * img);
-        RUN(conv2d64(M, blk.dsc, x, H, W, scb, RVC_ACT_NONE, nullptr, s));
+        T* scb = take<T>(sc, blk.c0.Co * img);
+        RUN(conv2d<T>(c, M, blk.sc, x, H, W, scb, RVC_ACT_NONE, nullptr, s));
         res = scb;
     }
-    RUN(conv2d64(M, blk.d3, h, H, W, out, RVC_ACT_RELU, res, s));
+    RUN(conv2d<T>(c, M, blk.c3, h, H, W, out, RVC_ACT_RELU, res, s));
     return RVC_OK;
 }
 
-// rm_one in f64: the same launch sequence as RMVPEAMD's f64 form, the salience rounded to f32 once
-int rm_one64(rvc_ctx* c, Rmvpe& M, Scratch& sc, const float* wav, int64_t N, float* sal, hipStream_t s) {
-    const int64_t F = 1 + N / kHop, Tp = 32 * ((F - 1) / 32 + 1);
-    double* mag = take64(sc, (int64_t)(kNfft / 2 + 1) * F);
-    RUN(rvc_stft_mag64(wav, M.window, mag, 1, N, F, kNfft, kHop, 0, 0, s));
-    double* mel = take64(sc, (int64_t)kMels * F);
+// mel -> U-Net -> BiGRU -> fc for one sequence (rmvpe.py f0_device up to the decode), the same launch sequence as
+// RMVPEAMD's form of that arithmetic; the salience is f32 in both (the f64 form rounds it once).  Every image's
+// zero border is written by its producer (the glue kernels, the 2-D convs): the arena needs no zero fill.
+template <typename T>
+int rm_one(rvc_ctx* c, Rmvpe& M, const RmNet<T>& N, Scratch& sc, const float* wav, int64_t n, float* sal,
+           hipStream_t s) {
+    const int64_t F = 1 + n / kHop, Tp = 32 * ((F - 1) / 32 + 1);
+    // MelSpectrogram.forward (RMVPE.py:162-181): |STFT| in f64 (rvc_stft_mag), then the mel GEMM + log
+    T* mag = take<T>(sc, (int64_t)(kNfft / 2 + 1) * F);
+    RUN(stft_mag(wav, M.window, mag, n, F, s));
+    T* mel = take<T>(sc, (int64_t)kMels * F);
     {
-        C64Opts o;
+        RmOpts<T> o;
         o.out_act = RVC_ACT_LOGCLAMP;
-        o.out_slope = 1e-5;
-        RUN(conv64(M, M.mel64, mag, F, mel, o, s));
+        o.out_slope = (T)1e-5;
+        RUN(run_conv(c, M, N.mel, mag, F, mel, o, s));
     }
+    // mel2hidden input image (RMVPE.py:210-213)
     int64_t H = Tp, W = kMels;
-    double* x = take64(sc, (H + 2) * (W + 2));
-    RUN(rvc_mel_image64(mel, x, 1, kMels, F, Tp, M.in_scale64, M.in_shift64, 0, 0, s));
+    T* xi = take<T>(sc, (H + 2) * (W + 2));
+    RUN(mel_image(mel, xi, F, Tp, N.in_scale, N.in_shift, s));
+    const T* x = xi;
+    // encoder (RMVPE.py:64-76): the last block of each level writes into the decoder's concat buffer
     struct Cat {
-        double* buf;
+        T* buf;
         int64_t C, H, W;
     };
     std::vector<Cat> cats;
-    int64_t C = M.enc[0][0].d0.Co;
-    const int nb = (int)M.enc[0].size();
-    for (size_t l = 0; l < M.enc.size(); ++l) {
+    int64_t C = N.enc[0][0].c0.Co;
+    const int nb = (int)N.enc[0].size();
+    for (size_t l = 0; l < N.enc.size(); ++l) {
         const int64_t img = (H + 2) * (W + 2);
-        double* cat = take64(sc, 2 * C * img);
+        T* cat = take<T>(sc, 2 * C * img);
         for (int b = 0; b < nb; ++b) {
-            double* out = b == nb - 1 ? cat + C * img : take64(sc, C * img);
-            MTRY(cbr_run64(M, sc, M.enc[l][b], x, H, W, out, s));
+            T* out = b == nb - 1 ? cat + C * img : take<T>(sc, C * img);
+            MTRY(cbr_run<T>(c, M, sc, N.enc[l][b], x, H, W, out, s));
             x = out;
         }
         cats.push_back({cat, C, H, W});
-        double* pooled = take64(sc, C * (H / 2 + 2) * (W / 2 + 2));
-        RUN(rvc_avgpool2_64(x, pooled, 1, C, H, W, 0, 0, s));
+        T* pooled = take<T>(sc, C * (H / 2 + 2) * (W / 2 + 2));
+        RUN(avgpool2(x, pooled, C, H, W, s));
         x = pooled;
         H /= 2;
         W /= 2;
         C *= 2;
     }
-    for (auto& layer : M.inter)
+    for (auto& layer : N.inter)
         for (auto& blk : layer) {
-            double* out = take64(sc, blk.d0.Co * (H + 2) * (W + 2));
-            MTRY(cbr_run64(M, sc, blk, x, H, W, out, s));
+            T* out = take<T>(sc, blk.c0.Co * (H + 2) * (W + 2));
+            MTRY(cbr_run<T>(c, M, sc, blk, x, H, W, out, s));
             x = out;
         }
-    for (size_t i = 0; i < M.dec_t.size(); ++i) {
+    // decoder (RMVPE.py:78-107)
+    for (size_t i = 0; i < N.dec_t.size(); ++i) {
         const Cat& ct = cats[cats.size() - 1 - i];
-        const ConvT2d& T2 = M.dec_t[i];
+        const ConvT2d<T>& T2 = N.dec_t[i];
         const int64_t wrap = W + 2, Lc = (H + 2) * wrap;
-        double* ph = take64(sc, 4 * T2.Co * Lc);
+        T* ph = take<T>(sc, 4 * T2.Co * Lc);
         for (int p = 0; p < 4; ++p) {
-            C64Opts o;
+            RmOpts<T> o;
             o.Lout = Lc;
             o.wrap = (int)wrap;
             o.out_act = RVC_ACT_RELU;
             o.ntoff = T2.ntap[p];
             for (int t = 0; t < T2.ntap[p]; ++t) o.toff[t] = (int)(T2.dy[p][t] * wrap + T2.dx[p][t]);
-            RUN(conv64(M, T2.ph64[p], x, Lc, ph + p * T2.Co * Lc, o, s));
+            RUN(run_conv(c, M, T2.ph[p], x, Lc, ph + p * T2.Co * Lc, o, s));
         }
-        RUN(rvc_interleave4_64(ph, ct.buf, 1, T2.Co, H, W, 0, 0, s));
+        RUN(interleave4(ph, ct.buf, T2.Co, H, W, s));
         x = ct.buf;
         H = ct.H;
         W = ct.W;
-        for (auto& blk : M.dec[i]) {
-            double* out = take64(sc, blk.d0.Co * (H + 2) * (W + 2));
-            MTRY(cbr_run64(M, sc, blk, x, H, W, out, s));
+        for (auto& blk : N.dec[i]) {
+            T* out = take<T>(sc, blk.c0.Co * (H + 2) * (W + 2));
+            MTRY(cbr_run<T>(c, M, sc, blk, x, H, W, out, s));
             x = out;
         }
     }
-    double* img = take64(sc, 3 * (H + 2) * (W + 2));
-    RUN(conv2d64(M, M.cnn64, x, H, W, img, RVC_ACT_NONE, nullptr, s));
-    double* seq = take64(sc, 3 * W * H);
-    RUN(rvc_img_to_seq64(img, seq, 1, 3, H, W, 0, 0, s));
-    double* gi = take64(sc, 1536 * Tp);
-    {
-        C64Opts o;
-        RUN(conv64(M, M.w_ih64, seq, Tp, gi, o, s));
-    }
-    double* y = take64(sc, 512 * Tp);
-    RUN(rvc_bigru64_batched(gi, 0, M.w_hh64, M.b_hh64, y, 0, M.gran, M.err, 1, Tp, s));
-    C64Opts o;
+    T* img = take<T>(sc, 3 * (H + 2) * (W + 2));
+    RUN(conv2d<T>(c, M, N.cnn, x, H, W, img, RVC_ACT_NONE, nullptr, s));
+    T* seq = take<T>(sc, 3 * W * H);
+    RUN(img_to_seq(img, seq, 3, H, W, s));
+    // BiGRU + Linear + sigmoid (RMVPE.py:254-260, 141)
+    T* gi = take<T>(sc, 1536 * Tp);
+    RUN(run_conv(c, M, N.w_ih, seq, Tp, gi, RmOpts<T>(), s));
+    T* y = take<T>(sc, 512 * Tp);
+    RUN(bigru(M, gi, N.w_hh, N.b_hh, y, Tp, s));
+    RmOpts<T> o;
     o.out_act = RVC_ACT_SIGMOID;
-    o.y_f32 = 1;
-    RUN(conv64(M, M.fc64, y, Tp, sal, o, s));
+    RUN(run_conv(c, M, N.fc, y, Tp, sal, o, s));
+    return RVC_OK;
+}
+
+// rvc_load_rmvpe's network: every weight in the arithmetic's form (mb: the mel basis [128][513][1])
+template <typename T>
+int load_net(rvc_ctx* c, Rmvpe& M, RmNet<T>& N, Params& P, const HostT& mb) {
+    HostT w, b;
+#define GET(k, t) MCHECK(P.get(k, t), "rvc_load_rmvpe: missing %s", P.missing.c_str())
+    MTRY(make_w(c, M, mb, kMels, kNfft / 2 + 1, 1, nullptr, nullptr, N.mel));
+    {
+        std::vector<double> s, t;
+        MTRY(fold_bn(P, "unet.encoder.bn", s, t));
+        N.in_scale = (T)s[0];
+        N.in_shift = (T)t[0];
+    }
+    const int nblk = 4;  // E2E(4, 1, (2, 2))
+    for (int l = 0; P.has("unet.encoder.layers." + std::to_string(l) + ".conv.0.conv.0.weight"); ++l) {
+        N.enc.emplace_back(nblk);
+        for (int bb = 0; bb < nblk; ++bb)
+            MTRY(make_cbr(c, M, P, "unet.encoder.layers." + std::to_string(l) + ".conv." + std::to_string(bb),
+                          N.enc.back()[bb]));
+    }
+    for (int l = 0; P.has("unet.intermediate.layers." + std::to_string(l) + ".conv.0.conv.0.weight"); ++l) {
+        N.inter.emplace_back(nblk);
+        for (int bb = 0; bb < nblk; ++bb)
+            MTRY(make_cbr(c, M, P, "unet.intermediate.layers." + std::to_string(l) + ".conv." + std::to_string(bb),
+                          N.inter.back()[bb]));
+    }
+    for (int l = 0; P.has("unet.decoder.layers." + std::to_string(l) + ".conv1.0.weight"); ++l) {
+        const std::string p = "unet.decoder.layers." + std::to_string(l);
+        N.dec_t.emplace_back();
+        MTRY(make_convT2d(c, M, P, p, N.dec_t.back()));
+        N.dec.emplace_back(nblk);
+        for (int bb = 0; bb < nblk; ++bb) MTRY(make_cbr(c, M, P, p + ".conv2." + std::to_string(bb), N.dec.back()[bb]));
+    }
+    MCHECK(N.enc.size() == 5 && N.dec.size() == 5 && N.enc[0][0].c0.Ci == 1,
+           "rvc_load_rmvpe: expected the E2E(4, 1, (2, 2)) U-Net (5 encoder / decoder levels)");
+    GET("cnn.weight", w);
+    GET("cnn.bias", b);
+    MTRY(make_conv2d(c, M, w, nullptr, to_f64(b.v), N.cnn));
+    const std::string g = "fc.0.gru.";
+    HostT wi, wir, bi, bir;
+    GET(g + "weight_ih_l0", wi);
+    GET(g + "weight_ih_l0_reverse", wir);
+    GET(g + "bias_ih_l0", bi);
+    GET(g + "bias_ih_l0_reverse", bir);
+    MCHECK(wi.dim(0) == 768 && wi.dim(1) == 384, "rvc_load_rmvpe: GRU(384, 256) expected");
+    wi.v.insert(wi.v.end(), wir.v.begin(), wir.v.end());
+    bi.v.insert(bi.v.end(), bir.v.begin(), bir.v.end());
+    const std::vector<double> bid = to_f64(bi.v);
+    MTRY(make_w(c, M, wi, 1536, 384, 1, nullptr, &bid, N.w_ih));
+    HostT wh, whr, bh, bhr;
+    GET(g + "weight_hh_l0", wh);
+    GET(g + "weight_hh_l0_reverse", whr);
+    GET(g + "bias_hh_l0", bh);
+    GET(g + "bias_hh_l0_reverse", bhr);
+    wh.v.insert(wh.v.end(), whr.v.begin(), whr.v.end());
+    bh.v.insert(bh.v.end(), bhr.v.begin(), bhr.v.end());
+    MTRY(upload_as(M, wh.v, &N.w_hh));
+    MTRY(upload_as(M, bh.v, &N.b_hh));
+    GET("fc.1.weight", w);
+    GET("fc.1.bias", b);
+    MCHECK(w.dim(0) == kClass && w.dim(1) == 512, "rvc_load_rmvpe: fc.1 must be Linear(512, 360)");
+    const std::vector<double> bd = to_f64(b.v);
+    MTRY(make_w(c, M, w, kClass, 512, 1, nullptr, &bd, N.fc));
+#undef GET
     return RVC_OK;
 }
 
@@ -800,7 +804,7 @@ extern "C" int rvc_load_rmvpe(rvc_ctx* c, const rvc_param* params, int n) {
     c->rm = new Rmvpe();
     Rmvpe& M = *c->rm;
     M.f64 = c->rm_prec == RVC_PREC_FP64;
-    HostT w, b;
+    HostT w;
 #define GET(k, t) MCHECK(P.get(k, t), "rvc_load_rmvpe: missing %s", P.missing.c_str())
     // constants: Hann window, mel basis (rmvpe.py __init__, melbasis.py)
     if (P.has("window")) {
@@ -843,87 +847,8 @@ extern "C" int rvc_load_rmvpe(rvc_ctx* c, const rvc_param* params, int n) {
         }
     }
     mb.shape.push_back(1);
-    if (M.f64) MTRY(make_w64(M, mb, kMels, kNfft / 2 + 1, 1, nullptr, nullptr, M.mel64));
-    else MTRY(make_conv(c, M, mb, nullptr, M.mel));
-    {
-        std::vector<double> s, t;
-        MTRY(fold_bn(P, "unet.encoder.bn", s, t));
-        M.in_scale = (float)s[0];
-        M.in_shift = (float)t[0];
-        M.in_scale64 = s[0];
-        M.in_shift64 = t[0];
-    }
-    const int nblk = 4;  // E2E(4, 1, (2, 2))
-    for (int l = 0; P.has("unet.encoder.layers." + std::to_string(l) + ".conv.0.conv.0.weight"); ++l) {
-        M.enc.emplace_back(nblk);
-        for (int bb = 0; bb < nblk; ++bb)
-            MTRY(make_cbr(c, M, P, "unet.encoder.layers." + std::to_string(l) + ".conv." + std::to_string(bb),
-                          M.enc.back()[bb]));
-    }
-    for (int l = 0; P.has("unet.intermediate.layers." + std::to_string(l) + ".conv.0.conv.0.weight"); ++l) {
-        M.inter.emplace_back(nblk);
-        for (int bb = 0; bb < nblk; ++bb)
-            MTRY(make_cbr(c, M, P, "unet.intermediate.layers." + std::to_string(l) + ".conv." + std::to_string(bb),
-                          M.inter.back()[bb]));
-    }
-    for (int l = 0; P.has("unet.decoder.layers." + std::to_string(l) + ".conv1.0.weight"); ++l) {
-        const std::string p = "unet.decoder.layers." + std::to_string(l);
-        M.dec_t.emplace_back();
-        MTRY(make_convT2d(c, M, P, p, M.dec_t.back()));
-        M.dec.emplace_back(nblk);
-        for (int bb = 0; bb < nblk; ++bb) MTRY(make_cbr(c, M, P, p + ".conv2." + std::to_string(bb), M.dec.back()[bb]));
-    }
-    MCHECK(M.enc.size() == 5 && M.dec.size() == 5 && (M.f64 ? M.enc[0][0].d0.Ci : M.enc[0][0].c0.Ci) == 1,
-           "rvc_load_rmvpe: expected the E2E(4, 1, (2, 2)) U-Net (5 encoder / decoder levels)");
-    GET("cnn.weight", w);
-    GET("cnn.bias", b);
-    if (M.f64) {
-        const std::vector<double> bd = to_f64(b.v);
-        MTRY(make_w64(M, w, w.dim(0), w.dim(1), (int)(w.dim(2) * w.dim(3)), nullptr, &bd, M.cnn64));
-    } else {
-        MTRY(make_conv2d(c, M, w, nullptr, b.v, M.cnn));
-    }
-    const std::string g = "fc.0.gru.";
-    HostT wi, wir, bi, bir;
-    GET(g + "weight_ih_l0", wi);
-    GET(g + "weight_ih_l0_reverse", wir);
-    GET(g + "bias_ih_l0", bi);
-    GET(g + "bias_ih_l0_reverse", bir);
-    MCHECK(wi.dim(0) == 768 && wi.dim(1) == 384, "rvc_load_rmvpe: GRU(384, 256) expected");
-    wi.v.insert(wi.v.end(), wir.v.begin(), wir.v.end());
-    wi.shape = {1536, 384, 1};
-    bi.v.insert(bi.v.end(), bir.v.begin(), bir.v.end());
-    if (M.f64) {
-        const std::vector<double> bd = to_f64(bi.v);
-        MTRY(make_w64(M, wi, 1536, 384, 1, nullptr, &bd, M.w_ih64));
-    } else {
-        MTRY(make_conv(c, M, wi, &bi, M.w_ih));
-    }
-    HostT wh, whr, bh, bhr;
-    GET(g + "weight_hh_l0", wh);
-    GET(g + "weight_hh_l0_reverse", whr);
-    GET(g + "bias_hh_l0", bh);
-    GET(g + "bias_hh_l0_reverse", bhr);
-    wh.v.insert(wh.v.end(), whr.v.begin(), whr.v.end());
-    bh.v.insert(bh.v.end(), bhr.v.begin(), bhr.v.end());
-    if (M.f64) {
-        MTRY(upload64(M, to_f64(wh.v), &M.w_hh64));
-        MTRY(upload64(M, to_f64(bh.v), &M.b_hh64));
-    } else {
-        MTRY(upload(M, wh.v, &M.w_hh));
-        MTRY(upload(M, bh.v, &M.b_hh));
-    }
-    GET("fc.1.weight", w);
-    GET("fc.1.bias", b);
-    MCHECK(w.dim(0) == kClass && w.dim(1) == 512, "rvc_load_rmvpe: fc.1 must be Linear(512, 360)");
-    w.shape.push_back(1);
-    if (M.f64) {
-        const std::vector<double> bd = to_f64(b.v);
-        MTRY(make_w64(M, w, kClass, 512, 1, nullptr, &bd, M.fc64));
-    } else {
-        MTRY(make_conv(c, M, w, &b, M.fc));
-    }
 #undef GET
+    MTRY(M.f64 ? load_net(c, M, M.n64, P, mb) : load_net(c, M, M.n32, P, mb));
     MTRY(dev_alloc(M, RVC_BIGRU64_GRAN_BYTES, &M.gran));
     MTRY(dev_alloc(M, 4, (void**)&M.err));
     MHIP(hipMemset(M.err, 0, 4));
@@ -944,7 +869,7 @@ extern "C" int rvc_rmvpe_forward(rvc_ctx* c, const float* wav, int64_t B, int64_
     // (rmvpe.py: self.precision); the f64 form has its own engine
     if (!M.f64) c->prec = c->rm_prec;
     auto one = [&](Scratch& scr, const float* x, float* sal) {
-        return M.f64 ? rm_one64(c, M, scr, x, N, sal, s) : rm_one(c, M, scr, x, N, sal, s);
+        return M.f64 ? rm_one(c, M, M.n64, scr, x, N, sal, s) : rm_one(c, M, M.n32, scr, x, N, sal, s);
     };
     Scratch sc;
     int rc = one(sc, wav, salience);

@@ -678,7 +678,10 @@ def stft_frames(x, win, out, N, F, nfft, hop):
 
 
 def stft_mag(x, win, mag, N, F, nfft, hop):
-    """|STFT| in f64, rounded once: x [N] or [B][N] -> mag [nfft/2+1][F] or [B][nfft/2+1][F]."""
+    """|STFT| in f64: x [N] or [B][N] -> mag [nfft/2+1][F] or [B][nfft/2+1][F], rounded once to f32, or unrounded
+    for an f64 ``mag`` (stft_mag64)."""
+    if mag.dtype == torch.float64:
+        return stft_mag64(x, win, mag, N, F, nfft, hop)
     B = x.shape[0] if x.dim() == 2 else 1
     K = nfft // 2 + 1
     if (x.shape[-1] < N or win.numel() < nfft or mag.numel() < B * K * F or mag.shape[-1] != F
@@ -699,32 +702,44 @@ def spec_mag(spec, mag, K, F):
     return mag
 
 
+# RMVPE's image glue (rmvpe.hip), f32 or f64 by the tensors' dtype, on one image or on [B][...] views (batch strides
+# from the views).  Every op that writes a bordered image writes its zero border too.
+def _glue(fn32, fn64, src, src_nd, src_n, dst, dst_nd, dst_n, *dims):
+    """src ([B] + src_nd dims, src_n elements each) -> dst: one launch of the batched f64 entry point, or the f32
+    entry point (one image per launch) clip by clip."""
+    B = src.shape[0] if src.dim() > src_nd else 1
+    if src.dtype != dst.dtype or _room(src) < B * src_n or _room(dst) < B * dst_n:
+        raise ValueError(fn32 + ": size or dtype mismatch")
+    lib = _lib.load()
+    if src.dtype == torch.float64:
+        check(getattr(lib, fn64)(_pd(src), _pd(dst), B, *dims, _bs(src, src_nd), _bs(dst, dst_nd), _stream()), fn64)
+    else:
+        for b in range(B):
+            check(getattr(lib, fn32)(_p(src[b] if src.dim() > src_nd else src),
+                                     _p(dst[b] if dst.dim() > dst_nd else dst), *dims, _stream()), fn32)
+    return dst
+
+
 def mel_image(mel, img, M, F, Tp, scale, shift):
-    if mel.numel() < M * F or img.numel() < (Tp + 2) * (M + 2):
-        raise ValueError("mel_image: size mismatch")
-    check(_lib.load().rvc_mel_image(_p(mel), _p(img), M, F, Tp, scale, shift, _stream()), "mel_image")
-    return img
+    """mel [(B)][M][F] -> bordered images [(B)][1][Tp+2][M+2]: reflect-padded frames, times scale plus shift."""
+    return _glue("rvc_mel_image", "rvc_mel_image64", mel, 2, M * F, img, 3, (Tp + 2) * (M + 2), M, F, Tp, scale, shift)
 
 
 def avgpool2(x, out, C, H, W):
-    if x.numel() < C * (H + 2) * (W + 2) or out.numel() < C * (H // 2 + 2) * (W // 2 + 2):
-        raise ValueError("avgpool2: size mismatch")
-    check(_lib.load().rvc_avgpool2(_p(x), _p(out), C, H, W, _stream()), "avgpool2")
-    return out
+    """AvgPool2d(2): bordered [(B)][C][H+2][W+2] -> bordered [(B)][C][H/2+2][W/2+2]."""
+    return _glue("rvc_avgpool2", "rvc_avgpool2_64", x, 3, C * (H + 2) * (W + 2), out, 3,
+                 C * (H // 2 + 2) * (W // 2 + 2), C, H, W)
 
 
 def interleave4(phases, out, C, H, W):
-    if phases.numel() < 4 * C * (H + 2) * (W + 2) or out.numel() < C * (2 * H + 2) * (2 * W + 2):
-        raise ValueError("interleave4: size mismatch")
-    check(_lib.load().rvc_interleave4(_p(phases), _p(out), C, H, W, _stream()), "interleave4")
-    return out
+    """phases [(B)][4][C][H+2][W+2] -> the first C channels of bordered out [(B)][*][2H+2][2W+2]."""
+    return _glue("rvc_interleave4", "rvc_interleave4_64", phases, 4, 4 * C * (H + 2) * (W + 2), out, 3,
+                 C * (2 * H + 2) * (2 * W + 2), C, H, W)
 
 
 def img_to_seq(img, x, C, H, W):
-    if img.numel() < C * (H + 2) * (W + 2) or x.numel() < C * W * H:
-        raise ValueError("img_to_seq: size mismatch")
-    check(_lib.load().rvc_img_to_seq(_p(img), _p(x), C, H, W, _stream()), "img_to_seq")
-    return x
+    """bordered [(B)][C][H+2][W+2] -> sequence rows [(B)][C*W][H]."""
+    return _glue("rvc_img_to_seq", "rvc_img_to_seq64", img, 3, C * (H + 2) * (W + 2), x, 2, C * W * H, C, H, W)
 
 
 def bigru(gi, whh, bhh, y, gran, err, T):
@@ -880,7 +895,8 @@ def _bs(t, nd):
 
 
 def stft_mag64(x, win, mag, N, F, nfft, hop):
-    """|STFT| in f64 (unrounded): x [N] or [B][N] f32 -> mag f64 [nfft/2+1][F] or [B][nfft/2+1][F]."""
+    """|STFT| in f64 (unrounded): x [N] or [B][N] f32 -> mag f64 [nfft/2+1][F] or [B][nfft/2+1][F].  Kept under its
+    own name (stft_mag reaches it for an f64 ``mag``): bench.py's roofline pass wraps it to count the STFT family."""
     B = x.shape[0] if x.dim() == 2 else 1
     K = nfft // 2 + 1
     if (x.shape[-1] < N or win.numel() < nfft or mag.numel() < B * K * F or mag.shape[-1] != F
@@ -891,43 +907,6 @@ def stft_mag64(x, win, mag, N, F, nfft, hop):
     check(_lib.load().rvc_stft_mag64(_p(x), _p(win), _pd(mag), B, N, F, nfft, hop, x.stride(0) if B > 1 else 0,
                                      mag.stride(0) if B > 1 else 0, _stream()), "stft_mag64")
     return mag
-
-
-def mel_image64(mel, img, M, F, Tp, scale, shift):
-    """mel [(B)][M][F] f64 -> interior of bordered images [(B)][1][Tp+2][M+2] f64 (reflect-padded frames)."""
-    B = mel.shape[0] if mel.dim() == 3 else 1
-    if mel.numel() < B * M * F or img.numel() < B * (Tp + 2) * (M + 2):
-        raise ValueError("mel_image64: size mismatch")
-    check(_lib.load().rvc_mel_image64(_pd(mel), _pd(img), B, M, F, Tp, scale, shift, _bs(mel, 2), _bs(img, 3),
-                                      _stream()), "mel_image64")
-    return img
-
-
-def avgpool2_64(x, out, C, H, W):
-    B = x.shape[0] if x.dim() == 4 else 1
-    if _room(x) < B * C * (H + 2) * (W + 2) or _room(out) < B * C * (H // 2 + 2) * (W // 2 + 2):
-        raise ValueError("avgpool2_64: size mismatch")
-    check(_lib.load().rvc_avgpool2_64(_pd(x), _pd(out), B, C, H, W, _bs(x, 3), _bs(out, 3), _stream()), "avgpool2_64")
-    return out
-
-
-def interleave4_64(phases, out, C, H, W):
-    """phases [(B)][4][C][H+2][W+2] -> the first C channels of bordered out [(B)][*][2H+2][2W+2]."""
-    B = phases.shape[0] if phases.dim() == 5 else 1
-    if _room(phases) < B * 4 * C * (H + 2) * (W + 2) or _room(out) < B * C * (2 * H + 2) * (2 * W + 2):
-        raise ValueError("interleave4_64: size mismatch")
-    check(_lib.load().rvc_interleave4_64(_pd(phases), _pd(out), B, C, H, W, _bs(phases, 4), _bs(out, 3), _stream()),
-          "interleave4_64")
-    return out
-
-
-def img_to_seq64(img, x, C, H, W):
-    B = img.shape[0] if img.dim() == 4 else 1
-    if _room(img) < B * C * (H + 2) * (W + 2) or _room(x) < B * C * W * H:
-        raise ValueError("img_to_seq64: size mismatch")
-    check(_lib.load().rvc_img_to_seq64(_pd(img), _pd(x), B, C, H, W, _bs(img, 3), _bs(x, 2), _stream()),
-          "img_to_seq64")
-    return x
 
 
 GRU64_GRAN = 16384 // 8  # int64 words of bigru64 hand-off scratch per sequence (RVC_BIGRU64_GRAN_BYTES)

@@ -10,7 +10,9 @@ into the convolutions on the host at load.  On the device:
   U-Net     images kept zero-bordered [C][H+2][W+2]; every 3x3 / 1x1 conv is the MFMA
             implicit-GEMM engine in 2-D mode (tap offsets + border masking), ReLU and the
             residual add fused; encoder skips are written straight into the decoder's concat
-            buffers; ConvTranspose2d = 4 phase convs + interleave4
+            buffers; ConvTranspose2d = 4 phase convs + interleave4.  Every image's zero border
+            is written by its producer (the 2-D convs, mel_image, avgpool2, interleave4), so
+            no image is zero-filled first
   head      cnn conv -> img_to_seq -> W_ih GEMM (both directions) -> bigru recurrence
             -> Linear 512->360 + sigmoid -> f64 decode + coarse pitch (rmvpe_decode)
 
@@ -22,7 +24,9 @@ rounds only the salience to f32 for the decode.  RMVPE's f0 is a per-frame decis
 clip the exact model's top two bins are 3.2e-6 apart at one frame, while every f32 evaluation errs by up to
 1.7e-4 (the reference's own at other thread counts included): only an f64 network takes the exact model's
 decisions everywhere.  "fp32sa" / any ops.PASSES name runs the f32 form (split-bf16 MFMA convs,
-f32 BiGRU) for A/B comparisons.
+f32 BiGRU) for A/B comparisons.  The two forms are one network: the same code below and the same glue kernels
+(rmvpe.hip, templated on the scalar type); they differ in the conv engine (``_conv``), the BiGRU entry point and
+the dtype of the tensors, by which the ops wrappers dispatch.
 """
 from __future__ import annotations
 
@@ -71,7 +75,7 @@ class _Conv2d:
     def __init__(self, w, b, device, f64=True):
         Co, Ci, kh, kw = w.shape
         self.Co, self.Ci, self.k, self.f64 = Co, Ci, kh, f64
-        self.v = None
+        self.v, self.wx, self.wx_nmf = None, None, 0
         if f64:
             self.w = pack_km(w.reshape(Co, Ci, kh * kw).double()).to(device)
             self.b = b.double().to(device) if b is not None else None
@@ -94,11 +98,15 @@ class _Conv2d:
             toff, pad = [0], 0
         if self.v is not None and ops.wino64_use(self.Ci, self.Co, H, W):
             return ops.wino64(x, self.v, self.Ci, self.Co, H, W, bias=self.b, out=out, **_batch_kw(x, out, kw), **kw)
-        if self.f64:
-            return ops.conv64(x, self.w, self.Ci, self.Co, self.k * self.k, bias=self.b, pad=pad, Lin=L, Lout=L,
-                              out=out, toff=toff, wrap=wrap, **_batch_kw(x, out, kw), **kw)
-        return ops.conv1d(x, self.w, self.Ci, self.Co, self.k * self.k, bias=self.b, pad=pad, Lin=L, Lout=L,
-                          out=out, toff=toff, wrap=wrap, wx=self.wx, wx_nmf=self.wx_nmf, **_batch_kw(x, out, kw), **kw)
+        return _conv(self.f64, x, self.w, self.Ci, self.Co, self.k * self.k, self.wx, self.wx_nmf, bias=self.b, pad=pad,
+                     Lin=L, Lout=L, out=out, toff=toff, wrap=wrap, **_batch_kw(x, out, kw), **kw)
+
+
+def _conv(f64, x, w, Ci, Co, K, wx, wx_nmf, **kw):
+    """The conv engine of the arithmetic: conv64, or conv1d with the weight's split-operand images."""
+    if f64:
+        return ops.conv64(x, w, Ci, Co, K, **kw)
+    return ops.conv1d(x, w, Ci, Co, K, wx=wx, wx_nmf=wx_nmf, **kw)
 
 
 def _batch_kw(x, out, kw):
@@ -144,17 +152,9 @@ class _ConvT2d:
         for i, (wp, taps, wx, wx_nmf) in enumerate(self.phases):
             toff = [dy * wrap + dx for dy, dx in taps]
             out = ph[:, i] if B else ph[0, i]
-            if self.f64:
-                ops.conv64(x, wp, self.Ci, self.Co, len(taps), bias=self.bias, pad=0, Lin=L, Lout=L, out=out,
-                           toff=toff, wrap=wrap, out_act=ACT_RELU, **_batch_kw(x, out, {}))
-            else:
-                ops.conv1d(x, wp, self.Ci, self.Co, len(taps), bias=self.bias, pad=0, Lin=L, Lout=L, out=out,
-                           toff=toff, wrap=wrap, out_act=ACT_RELU, wx=wx, wx_nmf=wx_nmf, **_batch_kw(x, out, {}))
-        if self.f64:
-            ops.interleave4_64(ph if B else ph[0], out_cat, self.Co, H, W)
-        else:
-            for b in range(B or 1):
-                ops.interleave4(ph[b], out_cat[b] if B else out_cat, self.Co, H, W)
+            _conv(self.f64, x, wp, self.Ci, self.Co, len(taps), wx, wx_nmf, bias=self.bias, pad=0, Lin=L, Lout=L,
+                  out=out, toff=toff, wrap=wrap, out_act=ACT_RELU, **_batch_kw(x, out, {}))
+        ops.interleave4(ph if B else ph[0], out_cat, self.Co, H, W)
 
 
 class RMVPEAMD:
@@ -221,7 +221,7 @@ class RMVPEAMD:
         N = audio.numel()
         F = 1 + N // HOP
         mag = torch.empty(NFFT // 2 + 1, F, device=audio.device, dtype=self.dt)
-        (ops.stft_mag64 if self.f64 else ops.stft_mag)(audio, self.window, mag, N, F, NFFT, HOP)
+        ops.stft_mag(audio, self.window, mag, N, F, NFFT, HOP)
         return self.mel(mag, out_act=ACT_LOGCLAMP, out_slope=1e-5)
 
     @_at_precision
@@ -230,7 +230,7 @@ class RMVPEAMD:
         B, N = xb.shape
         F = 1 + N // HOP
         mag = torch.empty(B, NFFT // 2 + 1, F, device=xb.device, dtype=self.dt)
-        (ops.stft_mag64 if self.f64 else ops.stft_mag)(xb, self.window, mag, N, F, NFFT, HOP)
+        ops.stft_mag(xb, self.window, mag, N, F, NFFT, HOP)
         return self.mel(mag, out_act=ACT_LOGCLAMP, out_slope=1e-5)
 
     def _cbr(self, blk, x, H, W, out):
@@ -255,28 +255,10 @@ class RMVPEAMD:
         F = mel.shape[-1]
         Tp = 32 * ((F - 1) // 32 + 1)
         mel = mel.to(self.dt).contiguous()  # a caller's f32 mel (the reference's mel2hidden input) in the f64 form
-        # (the f64 kernels write the zero border themselves: no zero-fill launch on the f0 chain)
-        x = (torch.empty if self.f64 else torch.zeros)(1, Tp + 2, N_MELS + 2, device=mel.device, dtype=self.dt)
-        (ops.mel_image64 if self.f64 else ops.mel_image)(mel, x, N_MELS, F, Tp, self.in_scale, self.in_shift)
+        # (the kernel writes the zero border itself: no zero-fill launch on the f0 chain)
+        x = torch.empty(1, Tp + 2, N_MELS + 2, device=mel.device, dtype=self.dt)
+        ops.mel_image(mel, x, N_MELS, F, Tp, self.in_scale, self.in_shift)
         return x, Tp
-
-    def _pool(self, x, pooled, C, H, W):
-        if self.f64:
-            ops.avgpool2_64(x, pooled, C, H, W)
-        elif x.dim() == 4:
-            for b in range(x.shape[0]):
-                ops.avgpool2(x[b], pooled[b], C, H, W)
-        else:
-            ops.avgpool2(x, pooled, C, H, W)
-
-    def _to_seq(self, img, seq, H, W):
-        if self.f64:
-            ops.img_to_seq64(img, seq, 3, H, W)
-        elif img.dim() == 4:
-            for b in range(img.shape[0]):
-                ops.img_to_seq(img[b], seq[b], 3, H, W)
-        else:
-            ops.img_to_seq(img, seq, 3, H, W)
 
     def _unet(self, x, H, bshape):
         """E2E up to the GRU input on bordered images x [(B)][1][H+2][130] -> cnn head rows [(B)][384][H]."""
@@ -286,16 +268,15 @@ class RMVPEAMD:
         C = 16
         for l in range(5):
             # cat[C:] is written whole by the encoder's last conv (border included), cat[:C] by the decoder's
-            # interleave (which writes its border in the f64 form); pooled by the f64 pooling, border included
-            alloc = torch.empty if self.f64 else torch.zeros
-            cat = alloc(*bshape, 2 * C, H + 2, W + 2, device=dev, dtype=self.dt)
+            # interleave and pooled by the pooling, both border included: no zero fill
+            cat = torch.empty(*bshape, 2 * C, H + 2, W + 2, device=dev, dtype=self.dt)
             for b, blk in enumerate(self.enc[l]):
                 out = cat[..., C:, :, :] if b == self.nb - 1 else \
                     torch.empty(*bshape, C, H + 2, W + 2, device=dev, dtype=self.dt)
                 x = self._cbr(blk, x, H, W, out)
             cats.append((cat, C, H, W))
-            pooled = alloc(*bshape, C, H // 2 + 2, W // 2 + 2, device=dev, dtype=self.dt)
-            self._pool(x, pooled, C, H, W)
+            pooled = torch.empty(*bshape, C, H // 2 + 2, W // 2 + 2, device=dev, dtype=self.dt)
+            ops.avgpool2(x, pooled, C, H, W)
             x, H, W = pooled, H // 2, W // 2
             C *= 2
         for layer in self.inter:
@@ -312,7 +293,7 @@ class RMVPEAMD:
         img = torch.empty(*bshape, 3, H + 2, W + 2, device=dev, dtype=self.dt)
         self.cnn(x, H, W, img)
         seq = torch.empty(*bshape, 3 * W, H, device=dev, dtype=self.dt)
-        self._to_seq(img, seq, H, W)
+        ops.img_to_seq(img, seq, 3, H, W)
         return seq
 
     @_at_precision
@@ -380,12 +361,8 @@ class RMVPEAMD:
         B, _, F = mel.shape
         Tp = 32 * ((F - 1) // 32 + 1)
         mel = mel.to(self.dt).contiguous()
-        x = (torch.empty if self.f64 else torch.zeros)(B, 1, Tp + 2, N_MELS + 2, device=dev, dtype=self.dt)
-        if self.f64:
-            ops.mel_image64(mel, x, N_MELS, F, Tp, self.in_scale, self.in_shift)
-        else:
-            for b in range(B):
-                ops.mel_image(mel[b], x[b], N_MELS, F, Tp, self.in_scale, self.in_shift)
+        x = torch.empty(B, 1, Tp + 2, N_MELS + 2, device=dev, dtype=self.dt)
+        ops.mel_image(mel, x, N_MELS, F, Tp, self.in_scale, self.in_shift)
         seq = self._unet(x, Tp, (B,))
         return self._head(seq, B, Tp), Tp
 

@@ -88,16 +88,14 @@ def test_contentvec_batched_matches_per_clip(models):
         assert err <= 2e-5 * max(1.0, f1.abs().max().item()), err
 
 
-def test_rmvpe_batched_matches_per_clip(models):
-    _, rm, _, vc = models
-    xs = clips(3, 4.0, 400)
+def _rmvpe_batched_case(rm, vc, xs):
     xp = torch.stack([vc.filt(x, vc.t_pad)[0] for x in xs])
     mel_b = rm.mel_spectrogram_batch(xp)
     sal_b, Tp = rm.salience_batch(mel_b)
     coarse_b, pitchf_b = rm.f0_device_batch(xp)
     import f0check
     _, _, f0_b, _ = rm.f0_device_batch(xp, want_f0=True, want_salience=True)
-    for b in range(3):
+    for b in range(len(xs)):
         mel = rm.mel_spectrogram(xp[b])
         # the |STFT| is per frame (f64 FFT) in both; the mel GEMM may sum in another split-K order
         assert (mel_b[b] - mel).abs().max().item() <= 1e-4
@@ -121,6 +119,19 @@ def test_rmvpe_batched_matches_per_clip(models):
             if t not in allowed:
                 assert abs(pitchf_b[b, t].item() - pitchf[t].item()) <= 1e-3 * max(1.0, pitchf[t].item()), t
     rm.check_error()
+
+
+def test_rmvpe_batched_matches_per_clip(models):
+    _, rm, _, vc = models
+    _rmvpe_batched_case(rm, vc, clips(3, 4.0, 400))
+
+
+def test_rmvpe_batched_matches_per_clip_f32_form(models):
+    """The f32 form's batched path (batched convs and BiGRU, image glue per clip) on two clips of 1.1 s: the
+    shortest round length above the 1 s of reflect padding that VC.filt puts on each side (it needs N > t_pad)."""
+    from rvc_amd.rmvpe import RMVPEAMD
+    rm = RMVPEAMD(synthetic.rmvpe_state_dict(72), DEV, precision="fp32sa")
+    _rmvpe_batched_case(rm, models[3], clips(2, 1.1, 400))
 
 
 def test_pipeline_batch_matches_per_clip(models):

@@ -159,6 +159,25 @@ def test_native_rmvpe_matches_golden_and_python(golden):
     assert torch.equal(both[0], sal[0]) and torch.equal(both[1], nat.salience(wav.flip(0))[0][0])
 
 
+def test_native_rmvpe_f32_form_matches_python(golden):
+    """The f32 form (rmvpe_precision="fp32sa") issues the Python f32 form's launches: bit-identical salience (1 s)."""
+    from rvc_amd import melbasis
+    from rvc_amd.native import NativeRMVPE
+    from rvc_amd.rmvpe import RMVPEAMD
+    sd = synthetic.rmvpe_state_dict(int(golden("rmvpe")["seed"]))
+    py = RMVPEAMD(sd, DEV, precision="fp32sa")
+    nat = NativeRMVPE(sd, DEV, window=torch.hann_window(1024),
+                      mel_basis=melbasis.mel_filterbank(16000, 1024, 128, 30, 8000), rmvpe_precision="fp32sa")
+    wav = torch.from_numpy(synthetic.synthetic_audio(1.0, seed=31)).float().to(DEV)
+    sal_py, Tp = py.salience(py.mel_spectrogram(wav))
+    sal, F = nat.salience(wav)
+    torch.cuda.synchronize()
+    nat.check()
+    py.check_error()
+    assert sal.shape == (1, 360, Tp) and F == 1 + wav.numel() // 160
+    assert torch.equal(sal[0], sal_py)
+
+
 def test_c_host_runs_the_synthesizer_through_the_header_alone(tmp_path):
     """examples/c_host/synth_demo (gcc, no Python / torch in the process) loads the .pth tensors from a
     safetensors export and runs rvc_synth_infer: bit-identical to NativeSynth on the same inputs and seed."""

@@ -16,21 +16,36 @@ def rms(a, b):
     return float(np.sqrt(np.mean((a - b) ** 2)))
 
 
-@pytest.fixture(scope="module")
-def model(golden):
+_MODELS = {}
+
+
+def _model(golden, precision):
     from rvc_amd.rmvpe import RMVPEAMD
     g = golden("rmvpe")
-    return RMVPEAMD(synthetic.rmvpe_state_dict(int(g["seed"])), DEV), g
+    if precision not in _MODELS:
+        _MODELS[precision] = RMVPEAMD(synthetic.rmvpe_state_dict(int(g["seed"])), DEV, precision=precision)
+    return _MODELS[precision], g
 
 
-def test_mel(model):
-    m, g = model
+@pytest.fixture(scope="module")
+def model(golden):
+    return _model(golden, "f64")
+
+
+@pytest.fixture(scope="module", params=["f64", "fp32sa"])
+def model_p(request, golden):
+    """The default f64 network and the f32 form (round 3's default, whose bars the three tests below still carry)."""
+    return _model(golden, request.param)
+
+
+def test_mel(model_p):
+    m, g = model_p
     mel = m.mel_spectrogram(torch.from_numpy(g["audio"]).float().to(DEV))
     assert rms(mel.unsqueeze(0), g["mel"]) < 1e-4
 
 
-def test_salience(model):
-    m, g = model
+def test_salience(model_p):
+    m, g = model_p
     mel = torch.from_numpy(g["mel"][0]).to(DEV)
     sal, Tp = m.salience(mel)
     F = mel.shape[-1]
@@ -41,8 +56,8 @@ def test_salience(model):
     assert rms(got, g["hidden"]) < 3e-5
 
 
-def test_f0_end_to_end(model):
-    m, g = model
+def test_f0_end_to_end(model_p):
+    m, g = model_p
     f0 = m.infer_from_audio(g["audio"], thred=0.03)
     assert f0.shape == g["f0"].shape
     assert np.max(np.abs(f0 - g["f0"])) < 1e-2
